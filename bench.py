@@ -8,6 +8,8 @@ a fixed prior of exactly N x G components and a fixed measurement set, so
 every step does identical work; the prior stays resident in HBM.
 
     python bench.py                      # N=1, config 3: 4096 x 512 x 64, CV + CPHD
+    python bench.py --full               # + cpu_baseline, config4_model and the copy ceiling of the roofline
+    python bench.py --dump-outputs DIR   # + the last timed step's state as DIR/<name>.npy
     python bench.py --config 2           # 1024 x 256 x 32, Ackerman + PHD
     python bench.py --config 1           # the CPU oracle alone over the reference's data (configs[0])
     torchrun --nproc-per-node N bench.py --gpus N   # weak scaling, particles sharded
@@ -166,6 +168,41 @@ def copy_bandwidth(dev, mib=1024, reps=10):
     return gbs
 
 
+DUMP_MAP_BYTES = 48 << 20  # --dump-outputs: the maps' share of its 64 MB
+
+
+def dump_outputs(dirpath, state, seed, rank=0):
+    """--dump-outputs: the state a caller of the timed path holds after its last
+    step (PHDFilter.export(): poses, log-weights, maps as CSR) as
+    DIR/<name>.npy, float32 (the index arrays float64).  Every particle's pose,
+    log-weight and map size is written; the maps (config 3: 4096 x ~570
+    components x 28 B, past the 64 MB this option may write) of a fixed sample
+    of particles, drawn once from `seed` in particle order until
+    DUMP_MAP_BYTES are filled: maps.npy holds their components back to back
+    (weight, mean[2], cov[4]), map_particles.npy their particle indices and
+    map_offsets.npy the CSR offsets into maps.npy."""
+    poses, lw, maps, offs = state
+    os.makedirs(dirpath, exist_ok=True)
+    n = len(lw)
+    sizes = np.diff(offs).astype(np.int64)
+    order = np.random.default_rng(seed).permutation(n)
+    fits = np.cumsum(sizes[order] * maps.dtype.itemsize) <= DUMP_MAP_BYTES
+    picked = np.sort(order[:int(fits.sum())])
+    parts = [maps[offs[p]:offs[p + 1]] for p in picked]
+    sample = np.concatenate(parts) if parts else maps[:0]
+    flat = np.concatenate([sample["weight"][:, None], sample["mean"], sample["cov"]], axis=1).astype(np.float32)
+    sample_offs = np.concatenate([[0], np.cumsum(sizes[picked])])
+    out = {"poses": np.stack([poses[k] for k in poses.dtype.names], axis=1).astype(np.float32),
+           "log_weights": np.asarray(lw, np.float32),
+           "map_sizes": sizes.astype(np.float64),
+           "map_particles": picked.astype(np.float64),
+           "map_offsets": sample_offs.astype(np.float64),
+           "maps": flat}
+    tag = f"_rank{rank}" if rank else ""
+    for name, a in out.items():
+        np.save(os.path.join(dirpath, f"{name}{tag}.npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -176,7 +213,14 @@ def main():
     ap.add_argument("--particles", type=int, default=0, help="override particles per GPU")
     ap.add_argument("--threads", type=int, default=0, help="threads per particle of the fused update (0 = auto)")
     ap.add_argument("--form", type=int, default=0, help="PHD update form: 0 auto, 1 one fused launch, 2 split (A + C)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, in runs of their own beside the "
+                         "timed steps: the CPU oracle's rate (cpu_baseline), config 4's own model beside a config-3 "
+                         "line (config4_model) and the device-copy ceiling of the roofline (copy_ceiling_gbs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the last timed step (poses, log-weights, map sizes, the maps of a "
+                         "fixed seeded sample of particles) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (gloo only to rehearse N>1 on one GPU)")
     ap.add_argument("--mode", choices=["replay", "sequence"], default="replay",
@@ -301,8 +345,8 @@ def main():
         else:
             _step_async(f, control, motion_ack, k)
 
-    # the achievable-bandwidth reference of the roofline (a 1 GiB device copy)
-    copy_gbs = copy_bandwidth(dev)
+    # the achievable-bandwidth reference of the roofline (a 1 GiB device copy; --full)
+    copy_gbs = copy_bandwidth(dev) if args.full else None
     # GPU clock warm-up before the warm-up steps: a cold GPU ramps its shader
     # clock over tens of ms, so after only the driver's 5 warm-up steps (1.5 ms
     # of work) its first 20 timed steps run ~6 % below the steady state (20
@@ -370,6 +414,8 @@ def main():
     slow = {"merge_fallbacks": f.merge_fallbacks(), "merge_pair_overflows": f.merge_pair_overflows(),
             "status_errors": f.status_errors(), "particle_updates": n * args.steps}
     f.check_errors()
+    if args.dump_outputs:  # (every rank its shard: <name>.npy on rank 0, <name>_rank<r>.npy beside it)
+        dump_outputs(args.dump_outputs, f.export(), seed, rank)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -458,7 +504,8 @@ def main():
     line["config"]["capacities"] = {"map": caps.map_capacity, "candidates": caps.candidate_capacity,
                                     "survivors": caps.survivor_capacity, "measurements": caps.max_measurements,
                                     "overflow_fallback": wide}
-    line["roofline"]["copy_ceiling_gbs"] = round(copy_gbs, 1)
+    if copy_gbs is not None:
+        line["roofline"]["copy_ceiling_gbs"] = round(copy_gbs, 1)
     line["config"]["gpu_clock_warmup"] = (f"{spin} bf16 8192^3 matrix products ({1e3 * t_spin:.0f} ms) before the "
                                           f"{args.warmup} warm-up steps" if spin > 0 else "none")
     if sharded is not None:
@@ -472,7 +519,7 @@ def main():
         line["config"]["pending_slots"] = st["pending_slots"]
         if hasattr(sharded, "close"):
             sharded.close()
-    if args.config == 3 and not args.no_config4_model:
+    if args.full and args.config == 3 and not args.no_config4_model:
         # the north-star ratio is config 4's own model on 8 GPUs
         # (Ackerman + PHD, one 32 768-particle filter) over config 3 on one GPU;
         # the driver's scaling curve is computed from `value` (config-3 shards),
@@ -483,7 +530,7 @@ def main():
             line["config4_model"] = _config4_model(args, dist, dev, world)
         except Exception as e:  # report, never fake (the main line stands)
             line["config4_model"] = {"value": None, "error": str(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # (N = 1 only: the bounded host sample)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:  # (N = 1 only: the bounded host sample)
         try:
             line["cpu_baseline"] = cpu_baseline(args.config, n, args.cpu_budget, births=bool(births))
         except Exception as e:  # report, never fake
@@ -522,6 +569,8 @@ def config1_line(args):
     for threads in sorted({1, n_all} | ({omp} if omp else set())):
         state, dt, S, rs = L.run(cfg, n=n, seed=SEED_C1, threads=threads)
         legs[threads] = (S / dt, dt, S, rs, int(np.diff(state[3]).max(initial=0)))
+        if args.dump_outputs and threads == 1:  # (the loop's final state)
+            dump_outputs(args.dump_outputs, state, SEED_C1)
     # value: the fastest leg (on the GPU box the 16-CPU share of OMP_NUM_THREADS
     # beats one thread per particle: 64 threads oversubscribe it)
     best = max(legs, key=lambda t: legs[t][0])

@@ -14,6 +14,6 @@ bash scripts/gpu_round_pmc.sh ${TAG}_pmc2 2 || exit $?
 bash scripts/profile_round.sh $TAG || exit $?
 for CFG in 4 5; do
   NP=$([ $CFG = 4 ] && echo 4096 || echo 8192)
-  timeout -k 10 300 python3 bench.py --config $CFG --particles $NP --steps 60 --warmup 10 > $OUT/c${CFG}_pergpu_bench.json 2> $OUT/c${CFG}_pergpu_bench.err || { tail -5 $OUT/c${CFG}_pergpu_bench.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --config $CFG --particles $NP --steps 60 --warmup 10 > $OUT/c${CFG}_pergpu_bench.json 2> $OUT/c${CFG}_pergpu_bench.err || { tail -5 $OUT/c${CFG}_pergpu_bench.err; exit 1; }
   head -c 400 $OUT/c${CFG}_pergpu_bench.json; echo
 done

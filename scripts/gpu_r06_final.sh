@@ -11,7 +11,7 @@ STAGE=${2:-all}
 OUT=gpurun_out/$T
 REPO=$(pwd)
 mkdir -p $OUT
-b() { local name=$1; shift; timeout -k 10 400 python3 bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err || { tail -5 $OUT/$name.err; exit 1; }; echo "$name: $(python3 -c "import json; d=json.load(open('$OUT/$name.json')); print(d['value'], d['unit'], d['roofline'] and d['roofline'].get('frac'))")"; }
+b() { local name=$1; shift; timeout -k 10 400 python3 bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err || { tail -5 $OUT/$name.err; exit 1; }; echo "$name: $(python3 -c "import json; d=json.load(open('$OUT/$name.json')); print(d['value'], d['unit'], d['roofline'] and d['roofline'].get('frac'))")"; }
 if [ "$STAGE" != b ]; then
 # (the PMC passes first: their report refreshes profiles/traffic_c3.json, which
 # the bench lines below carry as roofline.traffic)

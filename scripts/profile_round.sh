@@ -8,7 +8,7 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 for CFG in 2 3; do
-  timeout -k 10 300 python3 bench.py --config $CFG > "$OUT/c${CFG}_bench.json" 2> "$OUT/c${CFG}_bench.err" || exit $?
+  timeout -k 10 300 python3 bench.py --full --config $CFG > "$OUT/c${CFG}_bench.json" 2> "$OUT/c${CFG}_bench.err" || exit $?
   cat "$OUT/c${CFG}_bench.json"
   (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
       -d "$OUT/rp_c$CFG" -o run -- python3 "$REPO/bench.py" --config $CFG --steps 200 --warmup 20 --no-cpu-baseline \

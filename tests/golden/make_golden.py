@@ -121,6 +121,16 @@ def main():
                         controls=np.array(controls, dtype=np.float32),
                         meas=np.array(meas_flat, dtype=np.float32).reshape(-1, 2),
                         meas_offsets=np.array(meas_off, dtype=np.int64))
+    # the same data as shipped text (tests/test_io.py reads the loaders' input
+    # formats from it): the controls file whole, the measurements file's first
+    # 100 scans, and the shipped settings file (tests/test_capi.py)
+    import shutil
+    shutil.copyfile(os.path.join(REF_PY, "controls_synth.txt"), os.path.join(HERE, "controls_synth.txt"))
+    with open(os.path.join(REF_PY, "measurements_synth.txt")) as f, \
+            open(os.path.join(HERE, "measurements_synth_head.txt"), "w") as g:
+        g.writelines(f.readlines()[:100])
+    shutil.copyfile(os.path.join(os.path.dirname(REF_PY), "cfg", "config.cfg"),
+                    os.path.join(HERE, "reference_config.cfg"))
     # the reference's CV dataset (matlab/measurements_synth_cv.txt): '%' header, then
     # one step per line of range/bearing pairs; the first 40 steps
     cv_flat, cv_off = [], [0]

@@ -122,9 +122,8 @@ def test_config_loader(built, tmp_path):
 
 
 def test_reference_config_file_parses(built):
-    path = "/root/reference/cfg/config.cfg"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box)")
+    """The reference's shipped cfg/config.cfg (tests/golden/reference_config.cfg)."""
+    path = os.path.join(REPO, "tests", "golden", "reference_config.cfg")
     import phdslam
     c, d = phdslam.load_config(path)
     assert c.motionType == 1 and c.n_particles == 200 and abs(c.maxRange - 15) < 1e-6

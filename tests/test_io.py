@@ -3,7 +3,8 @@ and the writeLog writer of src/main.cpp:848-954, host-only entry points of
 libphdslam.so (include/phd_io.h).  No GPU.
 
 Golden anchors: the reference's shipped data files (python/controls_synth.txt,
-python/measurements_synth.txt) as committed in tests/golden/config1_data.npz,
+python/measurements_synth.txt) as committed in tests/golden/config1_data.npz
+(and as text: tests/golden/controls_synth.txt, measurements_synth_head.txt),
 and the writer's byte format = std::ostream default float formatting, which
 Python's "%g" reproduces (6 significant digits)."""
 import os
@@ -12,7 +13,8 @@ import numpy as np
 import pytest
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "config1_data.npz")
-REF_PY = "/root/reference/python"
+SHIPPED_CONTROLS = os.path.join(os.path.dirname(__file__), "golden", "controls_synth.txt")
+SHIPPED_MEAS_HEAD = os.path.join(os.path.dirname(__file__), "golden", "measurements_synth_head.txt")
 
 
 def _g(x):
@@ -52,21 +54,27 @@ def test_shipped_synth_data_matches_golden(built, tmp_path):
     no header) load to the committed config-1 fixture."""
     from phdslam import io
     d = np.load(GOLDEN)
-    if os.path.isdir(REF_PY):
-        cpath, mpath = os.path.join(REF_PY, "controls_synth.txt"), os.path.join(REF_PY, "measurements_synth.txt")
-    else:  # rewrite the fixture in the shipped formats
-        cpath, mpath = tmp_path / "c.txt", tmp_path / "m.txt"
-        with open(cpath, "w") as f:
-            for v, a in d["controls"].astype(np.float64):
-                f.write(f"{float(v)!r}, {float(a)!r}\n")
-        with open(mpath, "w") as f:
-            mo = d["meas_offsets"]
-            for s in range(len(mo) - 1):
-                f.write(" ".join(repr(float(x)) for x in d["meas"][mo[s]:mo[s + 1]].ravel()) + "\n")
+    mo = d["meas_offsets"]
+    # the shipped text itself: the controls file whole, the measurements file's
+    # first 100 scans (the whole file is past the size a fixture may have)
+    u = io.load_controls(SHIPPED_CONTROLS, flags=io.COMMAS)
+    np.testing.assert_array_equal(np.stack([u["v_encoder"], u["alpha"]], 1), d["controls"])
+    z, offs = io.load_measurements(SHIPPED_MEAS_HEAD, flags=io.PAIRS)
+    assert len(offs) - 1 == 100
+    np.testing.assert_array_equal(offs, mo[:101].astype(np.int32))
+    np.testing.assert_array_equal(np.stack([z["range"], z["bearing"]], 1), d["meas"][:offs[-1]])
+    assert (z["label"] == 0).all()
+    # every scan: the fixture rewritten in the shipped formats
+    cpath, mpath = tmp_path / "c.txt", tmp_path / "m.txt"
+    with open(cpath, "w") as f:
+        for v, a in d["controls"].astype(np.float64):
+            f.write(f"{float(v)!r}, {float(a)!r}\n")
+    with open(mpath, "w") as f:
+        for s in range(len(mo) - 1):
+            f.write(" ".join(repr(float(x)) for x in d["meas"][mo[s]:mo[s + 1]].ravel()) + "\n")
     u = io.load_controls(cpath, flags=io.COMMAS)
     np.testing.assert_array_equal(np.stack([u["v_encoder"], u["alpha"]], 1), d["controls"])
     z, offs = io.load_measurements(mpath, flags=io.PAIRS)
-    mo = d["meas_offsets"]
     steps = len(offs) - 1
     assert steps >= 1134
     np.testing.assert_array_equal(offs, mo[:steps + 1].astype(np.int32))
