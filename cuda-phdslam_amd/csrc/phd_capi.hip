@@ -23,6 +23,7 @@
 #include "phd_capi.h"
 #include "phd_kernels.h"
 #include "phd_mixed_k.h"
+#include "phd_trace.h"
 
 using namespace phd;
 
@@ -189,6 +190,21 @@ struct phd_ctx {
     float* d_mx_ekf = nullptr;
     float* d_mx_cand = nullptr;
     size_t mx_lds = 0;
+    // per-scan estimate trace (phd_trace_enable): device rings of `cap` entries,
+    // `count` appended so far (entry count % cap is written next), and the
+    // scratch the two stages of phd_trace.hip hand each other
+    struct {
+        int cap = 0, snap_cap = 0, K = 0;
+        unsigned flags = 0;
+        long count = 0;
+        phd_trace_record* d_rec = nullptr;
+        phd_gaussian2d* d_snap = nullptr;
+        float* d_card = nullptr;
+        float* d_card_all = nullptr;  // every particle's rows (the expected form, map_estimate & 2)
+        float* d_w = nullptr;
+        double* d_part = nullptr;
+        int* d_hand = nullptr;
+    } tr;
 };
 
 static int set_device(phd_ctx* c) {
@@ -389,6 +405,13 @@ static ZBlk zblk_layout() {
     return L;
 }
 
+static void trace_free(phd_ctx* c) {
+    void* ptrs[] = {c->tr.d_rec, c->tr.d_snap, c->tr.d_card, c->tr.d_card_all, c->tr.d_w, c->tr.d_part, c->tr.d_hand};
+    for (void* p : ptrs)
+        if (p) hipFree(p);
+    c->tr = {};
+}
+
 static int ctx_free(phd_ctx* c) {
     if (!c) return PHD_OK;
     hipSetDevice(c->device);
@@ -403,6 +426,7 @@ static int ctx_free(phd_ctx* c) {
                     c->d_mx_cand};
     for (void* p : ptrs)
         if (p) hipFree(p);
+    trace_free(c);
     if (c->eap) eap_free(c->eap);
     if (c->h_mig) hipHostFree(c->h_mig);
     if (c->h_zring) hipHostFree(c->h_zring);
@@ -1891,6 +1915,149 @@ int phd_predict_update(phd_ctx* ctx, const phd_ackerman_control* u, int do_predi
     return PHD_OK;
 }
 
+/* what the trace does not cover (phd_trace_enable, and again at every traced
+ * step: the configuration may change in between) */
+static int trace_supported(const phd_ctx* ctx) {
+    if (ctx->cfg.featureModel != PHD_FEATURE_STATIC)
+        return fail(PHD_E_UNSUPPORTED, "the estimate trace supports the static feature model only");
+    if (ctx->cfg.nPredictParticles > 1 || ctx->n != ctx->n_base)
+        return fail(PHD_E_UNSUPPORTED, "the estimate trace does not support n_predict_particles > 1");
+    if (ctx->d_map_x) return fail(PHD_E_UNSUPPORTED, "the estimate trace does not support migrated (sharded) slabs");
+    if ((ctx->tr.flags & PHD_TRACE_CARD_DIST) &&
+        (ctx->cfg.filterType != PHD_FILTER_CPHD || ctx->cfg.maxCardinality + 1 != ctx->tr.K))
+        return fail(PHD_E_UNSUPPORTED, "PHD_TRACE_CARD_DIST needs the CPHD configuration it was enabled with");
+    if (ctx->tr.d_card && (ctx->cfg.mapEstimate & 2) && !ctx->tr.d_card_all)
+        return fail(PHD_E_UNSUPPORTED, "map_estimate changed after phd_trace_enable: enable the trace again");
+    return PHD_OK;
+}
+
+/* One entry of the trace from the state between the update and the resample
+ * (phd_trace.hip): stream-ordered, nothing waits on the host. */
+static int trace_append(phd_ctx* ctx, uint64_t step) {
+    auto& T = ctx->tr;
+    const size_t slot = (size_t)(T.count % T.cap);
+    TraceArgs a{};
+    a.logw = ctx->d_logw;
+    a.pose = ctx->d_pose;
+    a.src = ctx->d_src;
+    a.map_in = ctx->d_map[ctx->cur];
+    a.size_in = ctx->d_size[ctx->cur];
+    a.map_x = ctx->d_map_x;
+    a.size_x = ctx->d_size_x;
+    a.n = ctx->n;
+    a.cap = ctx->cap.map_capacity;
+    a.step = step;
+    a.M = ctx->M;
+    a.has_meas = rs_mode(ctx);
+    a.resample_thresh = ctx->cfg.resampleThresh;
+    a.err = ctx->d_err;
+    a.w_norm = T.d_w;
+    a.part = T.d_part;
+    a.hand = T.d_hand;
+    a.rec = T.d_rec + slot;
+    a.snap = T.d_snap ? T.d_snap + slot * (size_t)T.snap_cap : nullptr;
+    a.snap_cap = T.snap_cap;
+    a.K = T.K;
+    trace_launch_stage1(a, ctx->stream);
+    if (T.d_card && ctx->cn_valid) {
+        float* entry = T.d_card + slot * (size_t)T.K;
+        if ((ctx->cfg.mapEstimate & 2) && ctx->n > 1) {  // Σ exp(w_n) cn_n (recoverSlamState's expected form)
+            hipLaunchKernelGGL(k_cphd_cardinality, dim3(ctx->n), dim3(256), 0, ctx->stream, (const int*)ctx->d_src,
+                               (const double*)ctx->d_cn_coef, (const double*)ctx->d_cn_x, ctx->cn_stride,
+                               ctx->d_lfact, T.K - 1, ctx->n, T.d_card_all);
+            a.card = entry;
+            a.card_all = T.d_card_all;
+        } else {  // the arg-max particle's row: stage 1 left its slab reference
+            hipLaunchKernelGGL(k_cphd_cardinality, dim3(1), dim3(256), 0, ctx->stream,
+                               (const int*)(T.d_hand + TRACE_H_SLAB), (const double*)ctx->d_cn_coef,
+                               (const double*)ctx->d_cn_x, ctx->cn_stride, ctx->d_lfact, T.K - 1, 1, entry);
+        }
+    }
+    trace_launch_stage2(a, ctx->stream);
+    HIPCHK(hipGetLastError());
+    T.count++;
+    return PHD_OK;
+}
+
+int phd_trace_enable(phd_ctx* ctx, int capacity, int map_snapshot_cap, unsigned flags) {
+    if (!ctx || capacity < 0 || map_snapshot_cap < 0) return fail(PHD_E_ARG, "bad arguments to phd_trace_enable");
+    if (set_device(ctx)) return PHD_E_HIP;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    trace_free(ctx);
+    if (capacity == 0) return PHD_OK;
+    if (!ctx->cfg_set) return fail(PHD_E_ARG, "phd_set_config not called");
+    if (flags & ~(unsigned)PHD_TRACE_CARD_DIST) return fail(PHD_E_ARG, "unknown trace flags");
+    auto& T = ctx->tr;
+    T.flags = flags;
+    T.K = (flags & PHD_TRACE_CARD_DIST) ? ctx->cfg.maxCardinality + 1 : 0;
+    int rc = trace_supported(ctx);
+    if ((flags & PHD_TRACE_CARD_DIST) && !rc && T.K < 1) rc = fail(PHD_E_ARG, "CPHD needs max_cardinality >= 0");
+    if (rc) {
+        T = {};
+        return rc;
+    }
+    const size_t N = (size_t)ctx->nmax;
+    hipError_t e = hipMalloc((void**)&T.d_rec, (size_t)capacity * sizeof(phd_trace_record));
+    if (e == hipSuccess) e = hipMalloc((void**)&T.d_w, N * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&T.d_part, ((N + TRACE_PB - 1) / TRACE_PB) * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&T.d_hand, TRACE_H_WORDS * sizeof(int));
+    if (e == hipSuccess && map_snapshot_cap > 0)
+        e = hipMalloc((void**)&T.d_snap, (size_t)capacity * map_snapshot_cap * sizeof(phd_gaussian2d));
+    if (e == hipSuccess && T.K) e = hipMalloc((void**)&T.d_card, (size_t)capacity * T.K * sizeof(float));
+    if (e == hipSuccess && T.K && (ctx->cfg.mapEstimate & 2))
+        e = hipMalloc((void**)&T.d_card_all, N * T.K * sizeof(float));
+    if (e == hipSuccess) e = hipMemsetAsync(T.d_rec, 0, (size_t)capacity * sizeof(phd_trace_record), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(T.d_hand, 0, TRACE_H_WORDS * sizeof(int), ctx->stream);
+    // status_errors counts from here: the counter as it stands is the baseline
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(T.d_hand + TRACE_H_ERRPREV, ctx->d_err + 3, sizeof(int), hipMemcpyDeviceToDevice,
+                           ctx->stream);
+    if (e == hipSuccess && T.d_snap)
+        e = hipMemsetAsync(T.d_snap, 0, (size_t)capacity * map_snapshot_cap * sizeof(phd_gaussian2d), ctx->stream);
+    if (e == hipSuccess && T.d_card) e = hipMemsetAsync(T.d_card, 0, (size_t)capacity * T.K * sizeof(float), ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        trace_free(ctx);
+        return fail(PHD_E_HIP, std::string("phd_trace_enable: ") + hipGetErrorString(e));
+    }
+    T.snap_cap = map_snapshot_cap;
+    T.cap = capacity;  // (on from here)
+    return PHD_OK;
+}
+
+int phd_trace_count(phd_ctx* ctx, long* written_total) {
+    if (!ctx || !written_total) return fail(PHD_E_ARG, "null argument");
+    *written_total = ctx->tr.count;
+    return PHD_OK;
+}
+
+int phd_trace_read(phd_ctx* ctx, long first, int count, phd_trace_record* records, phd_gaussian2d* maps,
+                   float* card) {
+    if (!ctx || count < 0 || (count > 0 && !records)) return fail(PHD_E_ARG, "bad arguments to phd_trace_read");
+    const auto& T = ctx->tr;
+    if (T.cap <= 0) return fail(PHD_E_ARG, "the estimate trace is off (phd_trace_enable)");
+    if (first < 0 || first + count > T.count) return fail(PHD_E_ARG, "trace records not written yet");
+    if (first < T.count - T.cap) return fail(PHD_E_ARG, "trace records already overwritten");
+    if (maps && !T.d_snap) return fail(PHD_E_ARG, "the trace has no map snapshots");
+    if (card && !T.d_card) return fail(PHD_E_ARG, "the trace has no cardinality distributions");
+    if (count == 0) return PHD_OK;
+    if (set_device(ctx)) return PHD_E_HIP;
+    // the range is one run of the ring, or two where it wraps
+    const size_t s0 = (size_t)(first % T.cap);
+    const size_t c0 = std::min((size_t)count, (size_t)T.cap - s0), c1 = (size_t)count - c0;
+    auto pull = [&](void* dst, const void* ring, size_t entry) -> hipError_t {
+        hipError_t e = hipMemcpyAsync(dst, (const char*)ring + s0 * entry, c0 * entry, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && c1)
+            e = hipMemcpyAsync((char*)dst + c0 * entry, ring, c1 * entry, hipMemcpyDeviceToHost, ctx->stream);
+        return e;
+    };
+    HIPCHK(pull(records, T.d_rec, sizeof(phd_trace_record)));
+    if (maps) HIPCHK(pull(maps, T.d_snap, (size_t)T.snap_cap * sizeof(phd_gaussian2d)));
+    if (card) HIPCHK(pull(card, T.d_card, (size_t)T.K * sizeof(float)));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PHD_OK;
+}
+
 int phd_step(phd_ctx* ctx, const phd_ackerman_control* u, int do_predict, uint64_t step, float* neff_out,
              int* resampled) {
     if (!ctx) return fail(PHD_E_ARG, "null ctx");
@@ -1909,7 +2076,15 @@ int phd_step(phd_ctx* ctx, const phd_ackerman_control* u, int do_predict, uint64
     // below.  Its workgroups wait out part C on their CUs, so only while part C
     // is a few rounds of resident workgroups (config 4's per-GPU shard, 2.7
     // rounds: 3 409 -> 3 504 steps/s; config 5's, 16 rounds: 674 -> 645)
-    const bool overlap = (cfg.filterType == PHD_FILTER_CPHD ? (PHD_RS_OVERLAP & 1) : ctx->upd_split && (PHD_RS_OVERLAP & 2)) &&
+    // a traced step (phd_trace_enable) reads the poses and the log-weights the
+    // resample rewrites: its resample runs after the update and the trace
+    const bool traced = ctx->tr.cap > 0;
+    if (traced) {
+        int rc0 = trace_supported(ctx);
+        if (rc0) return rc0;
+    }
+    const bool overlap = !traced &&
+                         (cfg.filterType == PHD_FILTER_CPHD ? (PHD_RS_OVERLAP & 1) : ctx->upd_split && (PHD_RS_OVERLAP & 2)) &&
                          ctx->n <= 4 * ctx->upd_resident && cfg.nPredictParticles <= 1 &&
                          ctx->n == ctx->n_base && ctx->n > 2 * RS_THREADS && fuse_max && ctx->M > 0 &&
                          cfg.featureModel == PHD_FEATURE_STATIC;
@@ -1944,6 +2119,10 @@ int phd_step(phd_ctx* ctx, const phd_ackerman_control* u, int do_predict, uint64
         // everything the caller enqueues next after it
         if (ov_launched) hipStreamWaitEvent(ctx->stream, ctx->ev_rs, 0);
         return rc;
+    }
+    if (traced) {
+        rc = trace_append(ctx, step);
+        if (rc) return rc;
     }
     if (cfg.nPredictParticles > 1 || ctx->n != ctx->n_base) {
         // live count above n_particles: the resample draws n_particles children
@@ -2665,6 +2844,9 @@ static int take_counter(phd_ctx* ctx, int k, int* count) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
     *count = v;
     HIPCHK(hipMemsetAsync(ctx->d_err + k, 0, sizeof(int), ctx->stream));
+    // (the trace's status_errors is the counter's growth per step: restart its baseline too)
+    if (k == 3 && ctx->tr.d_hand)
+        HIPCHK(hipMemsetAsync(ctx->tr.d_hand + TRACE_H_ERRPREV, 0, sizeof(int), ctx->stream));
     return PHD_OK;
 }
 

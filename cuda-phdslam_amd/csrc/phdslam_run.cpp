@@ -4,7 +4,7 @@
  * device-resident C-ABI loop (phd_step).
  *
  *   phdslam_run <config.cfg> [--data DIR] [--steps N] [--triples] [--header]
- *               [--log DIR] [--device-loop]
+ *               [--log DIR] [--device-loop] [--trace]
  *
  * Inputs (DATA = data_directory of the cfg, or --data), read by the
  * reference-format loaders of include/phd_io.h (main.cpp:147-245):
@@ -18,6 +18,11 @@
  * --log DIR writes DIR/state_estimateNNNNN.log every step (writeLog,
  * main.cpp:848-954): expected pose, the EAP (mapEstimate & 2) or MAP map,
  * log-weights, poses, resample indices, cardinality.
+ * --trace (single GPU, static feature model, n_predict_particles 1) runs the
+ * device loop free: phd_set_measurements + phd_step per scan with no read-back,
+ * the device-side estimate trace (phd_trace_enable) read once at the end and
+ * written to trajectory.txt (in --log DIR, else the working directory), one
+ * line per scan: scan, expected pose, MAP pose, nEff, resampled, cardinalities.
  *
  *   phdslam_run --synth C [--gpus N] [--particles P] [--steps K] [--replay]
  *               [--block-records R] [--resample-every] [--dump FILE]
@@ -210,7 +215,8 @@ static int run_synth_sharded(int argc, char** argv) {
 int main(int argc, char** argv) {
     if (argc >= 2 && !strcmp(argv[1], "--synth")) return run_synth_sharded(argc, argv);
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <config.cfg> [--data DIR] [--steps N] [--triples] [--device-loop]\n", argv[0]);
+        fprintf(stderr, "usage: %s <config.cfg> [--data DIR] [--steps N] [--triples] [--device-loop] [--trace]\n",
+                argv[0]);
         return 1;
     }
     SlamConfig config;
@@ -221,7 +227,7 @@ int main(int argc, char** argv) {
     }
     std::string data = data_dir;
     int n_steps = -1;
-    bool triples = false, device_loop = false, header = false;
+    bool triples = false, device_loop = false, header = false, trace = false;
     std::string log_dir;
     for (int i = 2; i < argc; i++) {
         if (!strcmp(argv[i], "--data") && i + 1 < argc) data = argv[++i];
@@ -230,6 +236,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--triples")) triples = true;
         else if (!strcmp(argv[i], "--header")) header = true;
         else if (!strcmp(argv[i], "--device-loop")) device_loop = true;
+        else if (!strcmp(argv[i], "--trace")) trace = device_loop = true;
     }
     if (!data.empty() && data.back() != '/') data += '/';
     const int base_flags = PHD_IO_COMMAS | PHD_IO_COMMENTS | (header ? PHD_IO_HEADER : 0);
@@ -335,7 +342,48 @@ int main(int argc, char** argv) {
         std::vector<ConstantVelocityState> st((size_t)N);
         std::vector<float> w((size_t)N), cn_all, cn;
         std::vector<int> sz((size_t)N), idx((size_t)N);
-        for (int n = 0; n < nSteps; n++) {
+        if (trace) {
+            // the free-running chain: phd_set_measurements + phd_step per scan, no
+            // read-back; the estimates come from the device trace, read once
+            if (phd_set_check_each_update(ctx, 0) != PHD_OK || phd_trace_enable(ctx, std::max(nSteps, 1), 0, 0) != PHD_OK) {
+                fprintf(stderr, "--trace: %s\n", phd_last_error());
+                return 1;
+            }
+            for (int n = 0; n < nSteps; n++) {
+                AckermanControl u{0.f, 0.f};
+                if (n > 0 && n - 1 < (int)allU.size()) u = allU[n - 1];
+                // (the predict's sub-steps are numbered as the loop below numbers them;
+                // the resample then draws at step n - 1 where that loop draws at n)
+                if (phd_set_measurements(ctx, allZ[n].data(), (int)allZ[n].size()) != PHD_OK ||
+                    phd_step(ctx, &u, n > 0, n > 0 ? (uint64_t)(n - 1) : 0, nullptr, nullptr) != PHD_OK) {
+                    fprintf(stderr, "step %d: %s\n", n, phd_last_error());
+                    return 1;
+                }
+            }
+            std::vector<phd_trace_record> rec((size_t)std::max(nSteps, 1));
+            if (phd_trace_read(ctx, 0, nSteps, rec.data(), nullptr, nullptr) != PHD_OK || phd_check_errors(ctx) != PHD_OK) {
+                fprintf(stderr, "--trace: %s\n", phd_last_error());
+                return 1;
+            }
+            const std::string path = (log_dir.empty() ? std::string(".") : log_dir) + "/trajectory.txt";
+            FILE* fp = fopen(path.c_str(), "w");
+            if (!fp) {
+                fprintf(stderr, "cannot write %s\n", path.c_str());
+                return 1;
+            }
+            fprintf(fp, "%% scan  expected pose (px py ptheta vx vy vtheta)  MAP pose (6)  nEff  resampled  "
+                        "card_expected  card_map  map_size\n");
+            for (int n = 0; n < nSteps; n++) {
+                const phd_trace_record& r = rec[n];
+                const ConstantVelocityState &e = r.expected_pose, &m = r.map_pose;
+                fprintf(fp, "%d %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %d %.9g %.9g %d\n", n,
+                        e.px, e.py, e.ptheta, e.vx, e.vy, e.vtheta, m.px, m.py, m.ptheta, m.vx, m.vy, m.vtheta, r.neff,
+                        r.resampled, r.card_expected, r.card_map, r.map_size);
+            }
+            fclose(fp);
+            printf("wrote %s (%d scans)\n", path.c_str(), nSteps);
+        }
+        for (int n = 0; n < nSteps && !trace; n++) {
             AckermanControl u{0.f, 0.f};
             if (n > 0 && n - 1 < (int)allU.size()) u = allU[n - 1];
             const int M = (int)allZ[n].size();

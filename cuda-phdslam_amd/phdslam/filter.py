@@ -11,8 +11,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .types import (ACKERMAN_NOISE, CV_NOISE, GAUSSIAN2D, GAUSSIAN4D, MEASUREMENT, POSE, AckermanControl, Capacity,
-                    SlamConfig, csr_from_maps)
+from .types import (ACKERMAN_NOISE, CV_NOISE, GAUSSIAN2D, GAUSSIAN4D, MEASUREMENT, POSE, TRACE_CARD_DIST,
+                    TRACE_RECORD, AckermanControl, Capacity, SlamConfig, csr_from_maps)
 
 
 def _ptr(a):
@@ -248,17 +248,58 @@ class PHDFilter:
         _lib.check(_lib.lib().phd_resample(self._h, _ptr(u), int(step), _ptr(idx)), "phd_resample")
         return idx
 
-    def step(self, control=None, do_predict=True, step=0):
-        """predict -> update -> normalize -> nEff -> resample-if-needed. Returns (neff, resampled)."""
+    def step(self, control=None, do_predict=True, step=0, readback=True):
+        """predict -> update -> normalize -> nEff -> resample-if-needed. Returns (neff, resampled).
+        readback=False enqueues the step without reading nEff and the decision back
+        (returns None; no host synchronisation once set_check_each_update(False)):
+        the estimate trace (enable_trace) records them on the device."""
         u = None
         if control is not None:
             v, alpha = control
             u = ctypes.byref(AckermanControl(float(alpha), float(v)))
+        if not readback:
+            _lib.check(_lib.lib().phd_step(self._h, u, 1 if do_predict else 0, int(step), None, None), "phd_step")
+            return None
         neff = ctypes.c_float()
         rs = ctypes.c_int()
         _lib.check(_lib.lib().phd_step(self._h, u, 1 if do_predict else 0, int(step), ctypes.byref(neff),
                                        ctypes.byref(rs)), "phd_step")
         return neff.value, bool(rs.value)
+
+    # -- per-scan estimate trace on the device ----------------------------
+    def enable_trace(self, capacity, map_snapshot_cap=0, card_dist=False):
+        """phd_trace_enable: every step() appends one TRACE_RECORD to a device ring
+        of `capacity` scans (0: off); map_snapshot_cap > 0 also keeps that many
+        components of the arg-max particle's map per scan, card_dist (CPHD) the
+        log cardinality distribution."""
+        _lib.check(_lib.lib().phd_trace_enable(self._h, int(capacity), int(map_snapshot_cap),
+                                               TRACE_CARD_DIST if card_dist else 0), "phd_trace_enable")
+        self._trace = (int(capacity), int(map_snapshot_cap),
+                       self.config.maxCardinality + 1 if card_dist and capacity else 0)
+
+    def trace_count(self):
+        """Scans appended since enable_trace (no synchronisation)."""
+        c = ctypes.c_long()
+        _lib.check(_lib.lib().phd_trace_count(self._h, ctypes.byref(c)), "phd_trace_count")
+        return c.value
+
+    def read_trace(self, first=None, count=None):
+        """Records [first, first + count) as a TRACE_RECORD array (default: every
+        scan the ring still holds); with snapshots / cardinality distributions
+        enabled returns (records, maps[count, map_snapshot_cap] GAUSSIAN2D or None,
+        card[count, max_cardinality + 1] float32 or None).  One synchronisation."""
+        cap, snap, K = getattr(self, "_trace", (0, 0, 0))
+        total = self.trace_count()
+        if first is None:
+            first = max(0, total - cap)
+        if count is None:
+            count = total - first
+        rec = np.zeros(max(count, 0), TRACE_RECORD)
+        maps = np.zeros((max(count, 0), snap), GAUSSIAN2D) if snap else None
+        card = np.zeros((max(count, 0), K), np.float32) if K else None
+        _lib.check(_lib.lib().phd_trace_read(self._h, int(first), int(count), _ptr(rec), _ptr(maps), _ptr(card)),
+                   "phd_trace_read")
+        return (rec, maps, card) if (snap or K) else rec
 
     def expected_pose(self):
         pose = np.zeros(1, POSE)

@@ -19,6 +19,15 @@ MEASUREMENT = np.dtype([("range", np.float32), ("bearing", np.float32), ("label"
 
 assert GAUSSIAN2D.itemsize == 28 and POSE.itemsize == 24 and MEASUREMENT.itemsize == 12
 
+# phd_trace_record (include/phd_types.h): one scan of the device-side estimate trace
+TRACE_RECORD = np.dtype([("step", np.uint64), ("n_live", np.int32), ("n_measure", np.int32),
+                         ("resampled", np.int32), ("neff", np.float32), ("expected_pose", POSE),
+                         ("map_particle", np.int32), ("map_pose", POSE), ("card_expected", np.float32),
+                         ("card_map", np.float32), ("map_size", np.int32), ("status_errors", np.int32),
+                         ("reserved", np.int32)])
+assert TRACE_RECORD.itemsize == 96
+TRACE_CARD_DIST = 1
+
 MOTION_CV = 0
 MOTION_ACKERMAN = 1
 
@@ -36,6 +45,21 @@ class Capacity(ctypes.Structure):
 _f = ctypes.c_float
 _i = ctypes.c_int
 _b = ctypes.c_bool
+
+
+class Pose(ctypes.Structure):
+    _fields_ = [("px", _f), ("py", _f), ("ptheta", _f), ("vx", _f), ("vy", _f), ("vtheta", _f)]
+
+
+class TraceRecord(ctypes.Structure):
+    """phd_trace_record (include/phd_types.h), 96 bytes; TRACE_RECORD is the same layout for arrays."""
+    _fields_ = [("step", ctypes.c_uint64), ("n_live", _i), ("n_measure", _i), ("resampled", _i), ("neff", _f),
+                ("expected_pose", Pose), ("map_particle", _i), ("map_pose", Pose), ("card_expected", _f),
+                ("card_map", _f), ("map_size", _i), ("status_errors", _i), ("reserved", _i)]
+
+
+assert ctypes.sizeof(TraceRecord) == TRACE_RECORD.itemsize
+assert all(getattr(TraceRecord, k).offset == TRACE_RECORD.fields[k][1] for k in TRACE_RECORD.names)
 
 
 class SlamConfig(ctypes.Structure):

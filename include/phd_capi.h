@@ -302,6 +302,42 @@ int phd_expected_map_dynamic(phd_ctx* ctx, phd_gaussian4d* out, long out_cap, lo
  * the single-workgroup fallback of non-finite inputs). */
 int phd_expected_map_groups(phd_ctx* ctx, int* groups);
 
+/* ---- per-scan estimate trace on the device ----
+ * With the trace on, every phd_step appends one phd_trace_record (phd_types.h)
+ * to a device ring: the estimates the synchronous entry points above return
+ * (phd_expected_pose, phd_neff, phd_cardinalities, phd_cardinality_distribution,
+ * the arg-max particle's row of phd_export_maps) at the point of the reference's
+ * loop where recoverSlamState takes them — after the normalisation, before the
+ * resample — computed by kernels on the context's stream (phd_trace.hip) with
+ * no host synchronisation.  Only phd_step appends; phd_predict_update,
+ * phd_normalize and phd_resample never do.  A traced step runs its resample
+ * after the update (not beside part C): the trace reads the poses and
+ * log-weights the resample rewrites.
+ *
+ * phd_trace_enable allocates a ring of `capacity` records; with
+ * map_snapshot_cap > 0 also capacity x map_snapshot_cap phd_gaussian2d (each
+ * scan's entry: the first map_snapshot_cap components of the arg-max particle's
+ * posterior map; the record's map_size holds the true count); with
+ * PHD_TRACE_CARD_DIST (CPHD only) also capacity x (max_cardinality+1) floats:
+ * the log cardinality distribution of the scan — with map_estimate & 2 the
+ * combination Σ_n exp(w_n) cn_n[k] recoverSlamState makes, else the arg-max
+ * particle's (zeros until a CPHD update has run).  capacity 0 turns the trace
+ * off and frees the rings; enabling again restarts the count at 0.
+ * PHD_E_UNSUPPORTED: feature_model 2, n_predict_particles > 1, a context that
+ * holds migrated (sharded) slabs, PHD_TRACE_CARD_DIST without CPHD.  Needs
+ * phd_set_config first.  Replay mode is supported (every record is the same).
+ * Synchronises (an allocation, not a step). */
+#define PHD_TRACE_CARD_DIST 1
+int phd_trace_enable(phd_ctx* ctx, int capacity, int map_snapshot_cap, unsigned flags);
+/* Records appended since phd_trace_enable (the host's count: no synchronisation). */
+int phd_trace_count(phd_ctx* ctx, long* written_total);
+/* Records [first, first + count) into records (count), maps (count x
+ * map_snapshot_cap, may be NULL) and card (count x (max_cardinality+1), may be
+ * NULL): one synchronisation, one copy per ring (two where the range wraps).
+ * PHD_E_ARG if part of the range has been overwritten or not written yet. */
+int phd_trace_read(phd_ctx* ctx, long first, int count, phd_trace_record* records, phd_gaussian2d* maps,
+                   float* card);
+
 /* Per-update timing of the fused kernel with HIP events recorded on the
  * context stream around each launch (ring of max_records pairs).
  * phd_update_timing synchronises, returns the summed ms over the recorded

@@ -115,6 +115,26 @@ typedef struct SlamConfig {
     bool saveAllMaps, savePrediction;
 } phd_slam_config;
 
+/* One scan of the device-side estimate trace (phd_trace_enable, phd_capi.h):
+ * the outputs of recoverSlamState (main.cpp:318-388) and the loop's nEff
+ * decision (main.cpp:1281-1289), taken from the normalised weights before the
+ * resample, written by phd_step without a host read-back. */
+typedef struct phd_trace_record {
+    uint64_t step;          /* the step argument of the phd_step call */
+    int n_live;             /* live particles of the scan */
+    int n_measure;          /* measurements of the scan */
+    int resampled;          /* the nEff decision of the step */
+    float neff;             /* as phd_neff */
+    phd_pose expected_pose; /* Σ exp(w)·state, as phd_expected_pose */
+    int map_particle;       /* first arg-max particle, as phd_expected_pose */
+    phd_pose map_pose;      /* its pose */
+    float card_expected;    /* Σ_n exp(w_n) Σ_j w_nj */
+    float card_map;         /* Σ_j w_j of the arg-max particle, as phd_cardinalities */
+    int map_size;           /* components of the arg-max particle's posterior map */
+    int status_errors;      /* particle-updates of this step that set a PHD_ST_* error bit */
+    int reserved;
+} phd_trace_record;
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #define PHD_STATIC_ASSERT(c, m) static_assert(c, m)
@@ -134,5 +154,14 @@ PHD_STATIC_ASSERT(offsetof(phd_slam_config, n_particles) == 196, "n_particles@19
 PHD_STATIC_ASSERT(offsetof(phd_slam_config, labeledMeasurements) == 292, "labeled@292");
 PHD_STATIC_ASSERT(offsetof(phd_slam_config, l) == 296, "l@296");
 PHD_STATIC_ASSERT(offsetof(phd_slam_config, saveAllMaps) == 320, "saveAllMaps@320");
+PHD_STATIC_ASSERT(sizeof(phd_trace_record) == 96, "phd_trace_record must be 96 B");
+PHD_STATIC_ASSERT(offsetof(phd_trace_record, n_live) == 8, "n_live@8");
+PHD_STATIC_ASSERT(offsetof(phd_trace_record, neff) == 20, "neff@20");
+PHD_STATIC_ASSERT(offsetof(phd_trace_record, expected_pose) == 24, "expected_pose@24");
+PHD_STATIC_ASSERT(offsetof(phd_trace_record, map_particle) == 48, "map_particle@48");
+PHD_STATIC_ASSERT(offsetof(phd_trace_record, map_pose) == 52, "map_pose@52");
+PHD_STATIC_ASSERT(offsetof(phd_trace_record, card_expected) == 76, "card_expected@76");
+PHD_STATIC_ASSERT(offsetof(phd_trace_record, map_size) == 84, "map_size@84");
+PHD_STATIC_ASSERT(offsetof(phd_trace_record, status_errors) == 88, "status_errors@88");
 
 #endif /* PHD_TYPES_H */
