@@ -22,6 +22,7 @@
 
 #include "phd_capi.h"
 #include "phd_kernels.h"
+#include "phd_slab.h"
 #include "phd_mixed_k.h"
 #include "phd_trace.h"
 
@@ -830,8 +831,7 @@ static int fetch_state(phd_ctx* ctx, HostState& h, bool with_maps) {
 }
 
 static inline int host_size(const HostState& h, int p) {
-    const int r = h.src[p];
-    return (r & PHD_SLAB_X) ? h.size_x[r & PHD_SLAB_MASK] : h.size_cur[r];
+    return slab_size(h.src[p], h.size_cur.data(), h.size_x.data());
 }
 
 int phd_export_particles(phd_ctx* ctx, int n, phd_pose* poses, float* logw, int* sizes) {
@@ -855,9 +855,7 @@ int phd_export_maps(phd_ctx* ctx, int n, const int* offsets, phd_gaussian2d* map
     int rc = fetch_state(ctx, h, true);
     if (rc) return rc;
     for (int p = 0; p < n; p++) {
-        const int r = h.src[p];
-        const bool in_x = (r & PHD_SLAB_X) != 0;
-        const float* s = (in_x ? h.map_x.data() : h.map_cur.data()) + (size_t)(r & PHD_SLAB_MASK) * 7 * cap;
+        const float* s = slab_map(h.src[p], h.map_cur.data(), h.map_x.data(), cap);
         const int sz = offsets[p + 1] - offsets[p];
         if (sz != host_size(h, p)) return fail(PHD_E_ARG, "offsets do not match the current map sizes");
         for (int k = 0; k < sz; k++) {
@@ -948,7 +946,7 @@ int phd_dynamic_sizes(phd_ctx* ctx, int* sizes) {
     HIPCHK(hipMemcpyAsync(dsz.data(), ctx->d_dsize[ctx->dcur], ctx->nmax * sizeof(int), hipMemcpyDeviceToHost,
                           ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int p = 0; p < n; p++) sizes[p] = dsz[src[p] & PHD_SLAB_MASK];
+    for (int p = 0; p < n; p++) sizes[p] = dsz[slab_index(src[p])];
     return PHD_OK;
 }
 
@@ -967,7 +965,7 @@ int phd_export_dynamic_maps(phd_ctx* ctx, int n, const int* offsets, phd_gaussia
                           ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     for (int p = 0; p < n; p++) {
-        const int r = src[p] & PHD_SLAB_MASK;
+        const int r = slab_index(src[p]);
         const int sz = offsets[p + 1] - offsets[p];
         if (sz != dsz[r]) return fail(PHD_E_ARG, "offsets do not match the current dynamic map sizes");
         const float* sl = all.data() + (size_t)r * PHD_DYN_FIELDS * dcap;

@@ -50,8 +50,7 @@
 
 #include "phd_detmath.h"
 #include "phd_kernels.h"
-
-#define NF 7 /* fields per component of a map slab (phd_kernels.hip) */
+#include "phd_slab.h"
 
 namespace phd {
 
@@ -60,8 +59,7 @@ __global__ void k_eap_sizes(const int* __restrict__ src, const int* __restrict__
                             const int* __restrict__ size_x, int n, int* __restrict__ sz) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
-    const int r = src[p];
-    sz[p] = (r & PHD_SLAB_X) ? size_x[r & PHD_SLAB_MASK] : size_in[r & PHD_SLAB_MASK];
+    sz[p] = slab_size(src[p], size_in, size_x);
 }
 
 /* Weighted components (SoA: w x y c00 c10 c01 c11), one block per particle;
@@ -80,8 +78,7 @@ __global__ void __launch_bounds__(256)
                  const int* __restrict__ off, const float* __restrict__ logw, int cap, long K,
                  float* __restrict__ comp, unsigned int* __restrict__ lam_bits, int* __restrict__ bad) {
     const int p = blockIdx.x;
-    const int r = src[p];
-    const float* s = ((r & PHD_SLAB_X) ? map_x : map_in) + (size_t)(r & PHD_SLAB_MASK) * NF * cap;
+    const float* s = slab_map(src[p], map_in, map_x, cap);
     const int o = off[p], sz = off[p + 1] - o;
     // map[i].weight *= exp(weights[n]) (main.cpp:302-303); D8: the deterministic exp shared with the oracle
     const float ew = phd_det_expf(logw[p]);

@@ -37,10 +37,6 @@
 #define PHD_ST_WAIT_TIMEOUT 64  /* an in-launch wait of the one-launch resample gave up: results invalid */
 #define PHD_ST_INFO (PHD_ST_SERIAL_MERGE | PHD_ST_PAIR_OVERFLOW) /* bits that are not errors */
 
-/* slab reference encoding in the index table: bit 30 selects the migration set X */
-#define PHD_SLAB_X 0x40000000
-#define PHD_SLAB_MASK 0x3fffffff
-
 #include <string>
 
 namespace phd {
@@ -520,12 +516,6 @@ __global__ void k_pack_blocks(const int* mig, int world, const int* send_src, in
 __global__ void k_unpack_blocks(const float* blocks, const float* ovf, int block_records, int overflow, const int* mig,
                                 int world, int rank, const int* recv_rec, int n, int cap, float* map_x, int* size_x,
                                 int* src, phd_pose* pose, float* logw, double* cn_x, int cn_stride);
-/* Particle record (cross-rank migration): [pose 6 | logw | size | map 7*cap]
- * 32-bit words, then (CPHD contexts) cn_stride doubles of cardinality
- * coefficients. */
-__host__ __device__ inline size_t record_words(int cap, int cn_stride) {
-    return 8 + (size_t)7 * cap + 2 * (size_t)cn_stride;
-}
 __global__ void k_unpack_slots(const float* rec, const int* slot_rec, int nslots, int first_slot, int cap, float* map_x,
                                int* size_x, int* src, phd_pose* pose, float* logw, double* cn_x, int cn_stride);
 __global__ void k_pack(const int* dcount, const int* src_idx, int count, int cap, const int* src, const float* map_in,

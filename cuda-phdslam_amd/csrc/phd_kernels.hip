@@ -28,8 +28,8 @@
 #include "phd_rng.h"
 #include "phd_devutil.h"
 #include "phd_cphd_terms.h"
-
-#define NF 7 /* fields per component */
+#include "phd_block.h"
+#include "phd_slab.h"
 
 /* Diagnostic build only (-DPHD_STAMPS): thread 0 of each workgroup records the
  * shader clock at phase boundaries into a.stamps[block][16]. */
@@ -1289,8 +1289,7 @@ __global__ void __launch_bounds__(256)
     if (p >= n) return;
     // coefficients live with the slab (row n = the posterior slab the update of
     // particle n wrote), so a resample's index remap carries them like the map
-    const int sref = src ? src[p] : p;
-    const double* co = ((sref & PHD_SLAB_X) ? cn_x : cn_coef) + (size_t)(sref & PHD_SLAB_MASK) * stride;
+    const double* co = slab_cn(src ? src[p] : p, cn_coef, cn_x, stride);
     const double ip0 = co[0], lq = co[1], lw = co[2], logW = co[3], W = co[4];
     const int M = (int)co[5];
     for (int k = threadIdx.x; k <= Nmax; k += blockDim.x) {
@@ -1438,11 +1437,13 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a) {
     const DevCfg& c = a.c;
     const int M = a.M;
     // slab of particle n: set `in` (or the migration set X) via the index table
+    // (decoded in place, not through slab_of: the helper's order of the size and
+    // map selects changes every update kernel's register allocation)
     const int sref = a.src ? a.src[n] : n;
     const bool in_x = (sref & PHD_SLAB_X) != 0;
     const int slab = sref & PHD_SLAB_MASK;
     const int G = in_x ? a.size_x[slab] : a.size_in[slab];
-    const G1 float* __restrict__ src = g1(uni_p((in_x ? a.map_x : a.map_in) + (size_t)slab * NF * a.cap));
+    const G1 float* __restrict__ src = g1(uni_p((in_x ? a.map_x : a.map_in) + (size_t)slab * PHD_NF * a.cap));
     // the step's births (CPHD: the previous scan's inverse measurements through
     // the prediction, phdfilter.cu.bak:738-870): prior components G .. Gp - 1
     // after the slab's G, placed by the classify below from the predicted pose
@@ -1450,14 +1451,14 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a) {
     // addBirths does, without copying the slab)
     const int Mb = a.births ? max(0, min(a.Mb, a.cap - G)) : 0;
     const int Gp = G + Mb;
-    G1 float* __restrict__ bdst = a.births ? g1(uni_p(a.births + (size_t)n * NF * a.cap)) : nullptr;
+    G1 float* __restrict__ bdst = a.births ? g1(uni_p(a.births + (size_t)n * PHD_NF * a.cap)) : nullptr;
     const G1 float* __restrict__ bsrc = a.births ? bdst - G : src;  // (indexed by prior component k >= G)
     // prior component k's field row: slab or birth slab
     auto prior = [&](int k) -> const G1 float* { return (k < G ? src : bsrc) + k; };
     X.K.src = src;
     X.K.bsrc = bsrc;
     X.K.G = G;
-    G1 float* __restrict__ dst = g1(uni_p(a.map_out + (size_t)n * NF * a.cap));
+    G1 float* __restrict__ dst = g1(uni_p(a.map_out + (size_t)n * PHD_NF * a.cap));
     // fused predict (phd_step): thread 0 advances this particle's pose through
     // the sub-steps (a call, so its registers do not count against the body's)
     phd_pose& s_pose = *(phd_pose*)(smem + L.pose);
@@ -1503,12 +1504,12 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a) {
     // counts and first list entries, all issued here: one round trip instead of
     // a chain of dependent ones after the measurement staging)
     constexpr int PF = 2;
-    float pf[PF][NF];
+    float pf[PF][PHD_NF];
 #pragma unroll
     for (int it = 0; it < PF; it++) {
         const int k = it * NT + tid;
 #pragma unroll
-        for (int f = 0; f < NF; f++) pf[it][f] = (k < G) ? src[f * a.cap + k] : 0.f;  // (births: placed below)
+        for (int f = 0; f < PHD_NF; f++) pf[it][f] = (k < G) ? src[f * a.cap + k] : 0.f;  // (births: placed below)
     }
     int hp_cnt[5] = {0, 0, 0, 0, 0};
     unsigned int hp_skey = 0;
@@ -1588,7 +1589,7 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a) {
         float2 tb = make_float2(0.f, 0.f);
         unsigned int win = 0;
         if (k < Gp) {
-            float v[NF];  // this component's fields: prefetched rows, else loaded here
+            float v[PHD_NF];  // this component's fields: prefetched rows, else loaded here
             if (k >= G) {
                 // the step's birth k - G, placed here from the predicted pose
                 // (birthsKernel, phdfilter.cu.bak:757-784) and kept in the birth slab
@@ -1604,16 +1605,16 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a) {
                 v[5] = cov[2];
                 v[6] = cov[3];
 #pragma unroll
-                for (int f = 0; f < NF; f++) bdst[f * a.cap + (k - G)] = v[f];
+                for (int f = 0; f < PHD_NF; f++) bdst[f * a.cap + (k - G)] = v[f];
             } else if (base == 0) {
 #pragma unroll
-                for (int f = 0; f < NF; f++) v[f] = pf[0][f];
+                for (int f = 0; f < PHD_NF; f++) v[f] = pf[0][f];
             } else if (base == NT) {
 #pragma unroll
-                for (int f = 0; f < NF; f++) v[f] = pf[1][f];
+                for (int f = 0; f < PHD_NF; f++) v[f] = pf[1][f];
             } else {
 #pragma unroll
-                for (int f = 0; f < NF; f++) v[f] = src[f * a.cap + k];
+                for (int f = 0; f < PHD_NF; f++) v[f] = src[f * a.cap + k];
             }
             const float dx = v[1] - pose.px;
             const float dy = v[2] - pose.py;
@@ -2036,20 +2037,20 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a) {
         float w = 0.f;
         bool keep = false;
         int k = 0;
-        float v[NF];
+        float v[PHD_NF];
         if (j < Gin) {
             k = s_in[j];
             // part C: the row prefetched at the start when the in-range list is
             // the identity there (all of the map in range), else loaded here
             if (PART == 2 && base == 0 && k == j && k < G) {
 #pragma unroll
-                for (int f = 0; f < NF; f++) v[f] = pf[0][f];
+                for (int f = 0; f < PHD_NF; f++) v[f] = pf[0][f];
             } else if (PART == 2 && base == NT && k == j && k < G) {
 #pragma unroll
-                for (int f = 0; f < NF; f++) v[f] = pf[1][f];
+                for (int f = 0; f < PHD_NF; f++) v[f] = pf[1][f];
             } else {
 #pragma unroll
-                for (int f = 0; f < NF; f++) v[f] = prior(k)[f * a.cap];
+                for (int f = 0; f < PHD_NF; f++) v[f] = prior(k)[f * a.cap];
             }
             // cphdUpdateKernel's exp(log w + lnd) as w e^lnd (D18)
             w = CPHD ? (v[0] > 0.f ? v[0] * ((const float*)(s_uni + 4))[1] : 0.f) : v[0] * (1 - c.pd);
@@ -2179,7 +2180,7 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a) {
         if (p < a.cap) {
             const int k = s_out[q];
 #pragma unroll
-            for (int f = 0; f < NF; f++) st_out(dst + f * a.cap + p, prior(k)[f * a.cap]);
+            for (int f = 0; f < PHD_NF; f++) st_out(dst + f * a.cap + p, prior(k)[f * a.cap]);
         }
     }
     int total = nout + Gout;
@@ -2273,24 +2274,6 @@ __global__ void __launch_bounds__(1024) k_update_cphd_c_1024(UpdateArgs a) { upd
 
 /* -------------------------------------------------------- normalise, nEff */
 
-template <typename T>
-__device__ __forceinline__ T block_reduce_1024(T v, T* s, bool is_max) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const T u = __shfl_xor(v, o, 64);
-        v = is_max ? (u > v ? u : v) : v + u;
-    }
-    if (lane == 0) s[wid] = v;
-    __syncthreads();
-    T r = is_max ? (T)-INFINITY : (T)0;
-    const int nw = (blockDim.x + 63) >> 6;
-    for (int w = 0; w < nw; w++) r = is_max ? (s[w] > r ? s[w] : r) : r + s[w];
-    __syncthreads();
-    return r;
-}
-
-
 /* logSumExp normalisation and nEff (standalone; the same block function as
  * k_normalize_resample, so both paths produce identical weights). */
 __device__ int normalize_block(float* __restrict__ logw, int n, const float* lse_override, float* __restrict__ out,
@@ -2322,36 +2305,6 @@ __global__ void __launch_bounds__(1024) k_lse_parts(const float* __restrict__ lo
 
 
 /* --------------------------------------------------------------- resample */
-
-/* 64-bit DPP helpers for the single-block resample (1024 threads). */
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ unsigned long long dpp_or_zero_u64(unsigned long long v) {
-    const unsigned int lo = (unsigned int)v, hi = (unsigned int)(v >> 32);
-    const unsigned int lo2 = (unsigned int)dpp_or_zero<CTRL, ROWMASK>((int)lo);
-    const unsigned int hi2 = (unsigned int)dpp_or_zero<CTRL, ROWMASK>((int)hi);
-    return ((unsigned long long)hi2 << 32) | lo2;
-}
-
-__device__ __forceinline__ unsigned long long wave_incl_scan_u64(unsigned long long x) {
-    x += dpp_or_zero_u64<0x111, 0xf>(x);
-    x += dpp_or_zero_u64<0x112, 0xf>(x);
-    x += dpp_or_zero_u64<0x114, 0xf>(x);
-    x += dpp_or_zero_u64<0x118, 0xf>(x);
-    x += dpp_or_zero_u64<0x142, 0xa>(x);
-    x += dpp_or_zero_u64<0x143, 0xc>(x);
-    return x;
-}
-
-__device__ __forceinline__ unsigned long long wave_incl_max_u64(unsigned long long x) {
-    unsigned long long y;
-    y = dpp_or_zero_u64<0x111, 0xf>(x); x = y > x ? y : x;
-    y = dpp_or_zero_u64<0x112, 0xf>(x); x = y > x ? y : x;
-    y = dpp_or_zero_u64<0x114, 0xf>(x); x = y > x ? y : x;
-    y = dpp_or_zero_u64<0x118, 0xf>(x); x = y > x ? y : x;
-    y = dpp_or_zero_u64<0x142, 0xa>(x); x = y > x ? y : x;
-    y = dpp_or_zero_u64<0x143, 0xc>(x); x = y > x ? y : x;
-    return x;
-}
 
 /* Stratified resample (main.cpp:453-501) by one 1024-thread block: fixed-point
  * CDF of det_expf terms (phd_detmath.h) in LDS (global `cdf_g` when n exceeds
@@ -2475,33 +2428,6 @@ __global__ void __launch_bounds__(RS_THREADS)
                    logw_out, new_logw);
 }
 
-/* The canonical order of the double sums of the normalisation (oracle D3: the
- * intended exact sum, up to one fixed reduction tree shared by every path).
- * The entries are cut into chunks of RS_THREADS; chunk c holds entries
- * c*1024 + t.  A chunk's sum is the wave_incl_scan_d total of each of its 16
- * waves, added in wave order; the chunk sums are added in chunk order.  The
- * single-block kernels (one thread per entry of every chunk) and the
- * multi-block sharded plan (one workgroup per chunk, k_rs_*) all evaluate
- * exactly this, so their weights agree bit for bit. */
-template <class F>
-__device__ double chunk_sum_block(int n, F&& f, double* s /* 32 doubles */) {
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-    double total = 0.0;
-    for (int c = 0; c * RS_THREADS < n; c++) {
-        const int i = c * RS_THREADS + t;
-        double x = i < n ? f(i) : 0.0;
-        x = wave_incl_scan_d(x);
-        double* sb = s + (c & 1) * 16;  // double-buffered: one barrier per chunk
-        if (lane == 63) sb[wid] = x;
-        __syncthreads();
-        double cs = 0.0;
-#pragma unroll
-        for (int w = 0; w < RS_THREADS / 64; w++) cs += sb[w];
-        total += cs;
-    }
-    return total;
-}
-
 /* logSumExp normalisation (phdfilter.cu:3748-3755), nEff (main.cpp:1281-1284)
  * and the resample decision (main.cpp:1286-1289) by one 1024-thread block;
  * thread t owns entries t, t+1024, ...; sums in the canonical chunk order.
@@ -2512,12 +2438,7 @@ __device__ int normalize_block(float* __restrict__ logw, int n, const float* lse
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
     float mx = -INFINITY;
     for (int i = t; i < n; i += RS_THREADS) mx = fmaxf(mx, logw[i]);
-    mx = wave_incl_max(mx);
-    if (lane == 63) s_f[wid] = mx;
-    __syncthreads();
-    mx = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < RS_THREADS / 64; w++) mx = fmaxf(mx, s_f[w]);
+    PHD_BLOCK_MAX_1024(mx, s_f, lane, wid);
     float lse;
     if (lse_override) {
         lse = *lse_override;
@@ -2533,8 +2454,8 @@ __device__ int normalize_block(float* __restrict__ logw, int n, const float* lse
             return (double)expf(2 * w);
         },
         s_d + 32);
-    const float neff = (float)(1.0 / (double)(float)s2 / (double)n);
-    const int resample = (has_meas == 2 || (has_meas && neff <= resample_thresh)) ? 1 : 0;  // 2: forced (n > 5N)
+    const float neff = neff_of(s2, n);
+    const int resample = resample_decision(neff, has_meas, resample_thresh);
     if (t == 0) {
         out[0] = lse;
         out[1] = neff;
@@ -2568,12 +2489,7 @@ __device__ int norm_resample_regs(float* __restrict__ logw, int n, float* __rest
     float mx = v[0];
 #pragma unroll
     for (int k = 1; k < PER; k++) mx = fmaxf(mx, v[k]);
-    mx = wave_incl_max(mx);
-    if (lane == 63) s_f[wid] = mx;
-    __syncthreads();
-    mx = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < W; w++) mx = fmaxf(mx, s_f[w]);
+    PHD_BLOCK_MAX_1024(mx, s_f, lane, wid);
     // chunk sums: wave totals of every chunk at once, then chunk by chunk in order
     auto chunk_total = [&](double (&x)[PER], double* sb) {
 #pragma unroll
@@ -2609,8 +2525,8 @@ __device__ int norm_resample_regs(float* __restrict__ logw, int n, float* __rest
         }
     }
     const double s2 = chunk_total(x, s_d + 16 * PER);
-    const float neff = (float)(1.0 / (double)(float)s2 / (double)n);
-    const int resample = (has_meas == 2 || (has_meas && neff <= resample_thresh)) ? 1 : 0;  // 2: forced (n > 5N)
+    const float neff = neff_of(s2, n);
+    const int resample = resample_decision(neff, has_meas, resample_thresh);
     if (t == 0) {
         out[0] = lse;
         out[1] = neff;
@@ -3117,12 +3033,7 @@ __device__ float rs_global_max(const float* __restrict__ part_max, int B, float*
     } else {
         for (int b = t; b < B; b += RS_THREADS) m = fmaxf(m, part_max[b]);
     }
-    m = wave_incl_max(m);
-    if (lane == 63) s_f[wid] = m;
-    __syncthreads();
-    m = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < RS_THREADS / 64; w++) m = fmaxf(m, s_f[w]);
+    PHD_BLOCK_MAX_1024(m, s_f, lane, wid);
     return m;
 }
 
@@ -3319,8 +3230,8 @@ __device__ __forceinline__ void rs_search_block(int N, int B, const double* part
     if (t == 0) {
         double s2 = 0.0;
         for (int b = 0; b < B; b++) s2 += __longlong_as_double((long long)S.end[b]);
-        const float neff = (float)(1.0 / (double)(float)s2 / (double)N);
-        const int resample = (has_meas == 2 || (has_meas && neff <= resample_thresh)) ? 1 : 0;  // 2: forced
+        const float neff = neff_of(s2, N);
+        const int resample = resample_decision(neff, has_meas, resample_thresh);
         S.flag = resample;
         S.cmin = INT_MAX;  // (the chunks this workgroup's strata fall in, below)
         S.cmax = -1;
@@ -3542,7 +3453,9 @@ __device__ void rs_step_block(const RsStepArgs& a, unsigned char* smem) {
             e += tot;
             s_end[c] = e;
         }
-        const float neff = (float)(1.0 / (double)(float)s2 / (double)N);
+        const float neff = neff_of(s2, N);
+        // (spelt out, not resample_decision: as arguments both of a's words are
+        // loaded up front, which changes this out-of-line function's code)
         const int resample = (a.has_meas == 2 || (a.has_meas && neff <= a.resample_thresh)) ? 1 : 0;
         s_i[0] = resample;
         s_i[1] = (int)(0xffffffffu - (unsigned)(km & 0xffffffffull));
@@ -3914,13 +3827,11 @@ __global__ void __launch_bounds__(256)
     if ((int)blockIdx.x >= n) return;
     const int j = slots ? slots[blockIdx.x] : (int)blockIdx.x;
     __shared__ int s_rank[257];
-    const int sref = src[j];
-    const bool in_x = (sref & PHD_SLAB_X) != 0;
-    const int sl = sref & PHD_SLAB_MASK;
-    const int G = in_x ? size_x[sl] : size_in[sl];
-    const float* s = (in_x ? map_x : map_in) + (size_t)sl * NF * cap;
-    float* d = map_out + (size_t)j * NF * cap;
-    for (int f = 0; f < NF; f++)
+    const Slab prior = slab_of(src[j], map_in, size_in, map_x, size_x, cap);
+    const int G = prior.size;
+    const float* s = prior.map;
+    float* d = map_out + (size_t)j * PHD_NF * cap;
+    for (int f = 0; f < PHD_NF; f++)
         for (int k = threadIdx.x; k < G; k += blockDim.x) d[f * cap + k] = s[f * cap + k];
     if (threadIdx.x == 0) {  // order-preserving ranks of the birth measurements
         int r = 0;
@@ -3949,7 +3860,7 @@ __global__ void __launch_bounds__(256)
     if (threadIdx.x == 0) {
         const int tot = G + s_rank[M];
         size_out[j] = min(tot, cap);
-        if (slots) src[j] = j;  // (every lane read sref before the barrier above)
+        if (slots) src[j] = j;  // (every lane read src[j] before the barrier above)
         if (tot > cap) {
             status[j] |= PHD_ST_MAP_OVERFLOW;
             atomicOr(err, PHD_ST_MAP_OVERFLOW);
@@ -3958,8 +3869,7 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-/* Particle record: [pose(6f) | logw | size | map 7*cap] as 32-bit words.
- * `dcount` (device) overrides `count` when given (records beyond it are not
+/* `dcount` (device) overrides `count` when given (records beyond it are not
  * written); the grid strides over records.  `logw_set` != 0 writes `logw_value`
  * as the record's log-weight (a sharded resample's -log N). */
 __global__ void __launch_bounds__(256)
@@ -3973,24 +3883,8 @@ __global__ void __launch_bounds__(256)
     for (int r = blockIdx.x; r < count; r += gridDim.x) {
         const int p = src_idx[r];
         const int sref = src[p];
-        const bool in_x = (sref & PHD_SLAB_X) != 0;
-        const int sl = sref & PHD_SLAB_MASK;
-        float* o = rec + (size_t)r * rw;
-        const int sz = in_x ? size_x[sl] : size_in[sl];
-        if (threadIdx.x == 0) {
-            const float* ps = (const float*)&pose[p];
-            for (int k = 0; k < 6; k++) o[k] = ps[k];
-            o[6] = logw_set ? logw_value : logw[p];
-            ((int*)o)[7] = sz;
-        }
-        const float* s = (in_x ? map_x : map_in) + (size_t)sl * NF * cap;
-        for (int f = 0; f < NF; f++)
-            for (int k = threadIdx.x; k < sz; k += blockDim.x) o[8 + f * cap + k] = s[f * cap + k];
-        if (cn_stride) {  // CPHD cardinality coefficients travel with the particle
-            const double* cs = (in_x ? cn_x : cn) + (size_t)sl * cn_stride;
-            double* co = (double*)(o + 8 + (size_t)NF * cap);
-            for (int k = threadIdx.x; k < cn_stride; k += blockDim.x) co[k] = cs[k];
-        }
+        record_write(rec + (size_t)r * rw, cap, cn_stride, &pose[p], logw_set ? logw_value : logw[p],
+                     slab_of(sref, map_in, size_in, map_x, size_x, cap), slab_cn(sref, cn, cn_x, cn_stride));
     }
 }
 
@@ -4003,23 +3897,8 @@ __global__ void __launch_bounds__(256)
     if (r >= count) return;
     const int p = dst_idx[r];
     const int xs = x_slot ? x_slot[r] : r;
-    const size_t rw = record_words(cap, cn_stride);
-    const float* o = rec + (size_t)r * rw;
-    const int sz = min(max(((const int*)o)[7], 0), cap);  // a record never carries more than cap
-    if (threadIdx.x == 0) {
-        float* pd = (float*)&pose[p];
-        for (int k = 0; k < 6; k++) pd[k] = o[k];
-        logw[p] = o[6];
-        size_x[xs] = sz;
-        src[p] = xs | PHD_SLAB_X;
-    }
-    float* d = map_x + (size_t)xs * NF * cap;
-    for (int f = 0; f < NF; f++)
-        for (int k = threadIdx.x; k < sz; k += blockDim.x) d[f * cap + k] = o[8 + f * cap + k];
-    if (cn_stride) {
-        const double* ci = (const double*)(o + 8 + (size_t)NF * cap);
-        for (int k = threadIdx.x; k < cn_stride; k += blockDim.x) cn_x[(size_t)xs * cn_stride + k] = ci[k];
-    }
+    const float* o = rec + (size_t)r * record_words(cap, cn_stride);
+    record_read(o, cap, cn_stride, p, xs, true, map_x, size_x, src, pose, logw, cn_x);
 }
 
 /* Receive side of a sharded resample: slot first_slot + i takes record
@@ -4033,24 +3912,8 @@ __global__ void __launch_bounds__(256)
     if (i >= nslots) return;
     const int r = slot_rec[i];
     const int p = first_slot + i;
-    const size_t rw = record_words(cap, cn_stride);
-    const float* o = rec + (size_t)r * rw;
-    const int sz = min(max(((const int*)o)[7], 0), cap);
-    if (threadIdx.x == 0) {
-        float* pd = (float*)&pose[p];
-        for (int k = 0; k < 6; k++) pd[k] = o[k];
-        logw[p] = o[6];
-        src[p] = r | PHD_SLAB_X;
-    }
-    if (i > 0 && slot_rec[i - 1] == r) return;
-    if (threadIdx.x == 0) size_x[r] = sz;
-    float* dd = map_x + (size_t)r * NF * cap;
-    for (int f = 0; f < NF; f++)
-        for (int k = threadIdx.x; k < sz; k += blockDim.x) dd[f * cap + k] = o[8 + f * cap + k];
-    if (cn_stride) {
-        const double* ci = (const double*)(o + 8 + (size_t)NF * cap);
-        for (int k = threadIdx.x; k < cn_stride; k += blockDim.x) cn_x[(size_t)r * cn_stride + k] = ci[k];
-    }
+    const float* o = rec + (size_t)r * record_words(cap, cn_stride);
+    record_read(o, cap, cn_stride, p, r, !(i > 0 && slot_rec[i - 1] == r), map_x, size_x, src, pose, logw, cn_x);
 }
 
 /* The sender's records in fixed blocks: record t of send_src goes to rank d
@@ -4089,23 +3952,8 @@ __global__ void __launch_bounds__(256)
         }
         const int p = send_src[t];
         const int sref = src[p];
-        const bool in_x = (sref & PHD_SLAB_X) != 0;
-        const int sl = sref & PHD_SLAB_MASK;
-        const int sz = in_x ? size_x[sl] : size_in[sl];
-        if (threadIdx.x == 0) {
-            const float* ps = (const float*)&pose[p];
-            for (int k = 0; k < 6; k++) o[k] = ps[k];
-            o[6] = logw_value;
-            ((int*)o)[7] = sz;
-        }
-        const float* sp = (in_x ? map_x : map_in) + (size_t)sl * NF * cap;
-        for (int f = 0; f < NF; f++)
-            for (int k = threadIdx.x; k < sz; k += blockDim.x) o[8 + f * cap + k] = sp[f * cap + k];
-        if (cn_stride) {
-            const double* cs = (in_x ? cn_x : cn) + (size_t)sl * cn_stride;
-            double* co = (double*)(o + 8 + (size_t)NF * cap);
-            for (int k = threadIdx.x; k < cn_stride; k += blockDim.x) co[k] = cs[k];
-        }
+        record_write(o, cap, cn_stride, &pose[p], logw_value, slab_of(sref, map_in, size_in, map_x, size_x, cap),
+                     slab_cn(sref, cn, cn_x, cn_stride));
     }
 }
 
@@ -4138,23 +3986,8 @@ __global__ void __launch_bounds__(256)
         const int r = rho - first;
         if ((r >= K) != (overflow != 0)) continue;  // the other pass's record
         const float* o = r < K ? blocks + ((size_t)s * K + r) * rw : ovf + (size_t)(ofirst + r - K) * rw;
-        const int p = d + i;
-        const int sz = min(max(((const int*)o)[7], 0), cap);
-        if (threadIdx.x == 0) {
-            float* pd = (float*)&pose[p];
-            for (int k = 0; k < 6; k++) pd[k] = o[k];
-            logw[p] = o[6];
-            src[p] = rho | PHD_SLAB_X;
-        }
-        if (i > 0 && recv_rec[i - 1] == rho) continue;
-        if (threadIdx.x == 0) size_x[rho] = sz;
-        float* dd = map_x + (size_t)rho * NF * cap;
-        for (int f = 0; f < NF; f++)
-            for (int k = threadIdx.x; k < sz; k += blockDim.x) dd[f * cap + k] = o[8 + f * cap + k];
-        if (cn_stride) {
-            const double* ci = (const double*)(o + 8 + (size_t)NF * cap);
-            for (int k = threadIdx.x; k < cn_stride; k += blockDim.x) cn_x[(size_t)rho * cn_stride + k] = ci[k];
-        }
+        record_read(o, cap, cn_stride, d + i, rho, !(i > 0 && recv_rec[i - 1] == rho), map_x, size_x, src, pose, logw,
+                    cn_x);
     }
 }
 
@@ -4163,41 +3996,12 @@ __global__ void __launch_bounds__(256)
 __global__ void __launch_bounds__(1024)
     k_expected_pose(const float* __restrict__ logw, const phd_pose* __restrict__ pose, int n, float* __restrict__ out) {
     __shared__ double s[32];
-    double acc[6] = {0, 0, 0, 0, 0, 0};
-    float bw = -FLT_MAX;
-    int bi = INT_MAX;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const float w = logw[i];
-        const float ew = expf(w);
-        const float* ps = (const float*)&pose[i];
-        for (int k = 0; k < 6; k++) acc[k] += (double)(ew * ps[k]);
-        if (w > bw) {
-            bw = w;
-            bi = i;
-        }
+    float ep[6];
+    const int best = expected_pose_block(n, [&](int i) { return logw[i]; }, pose, ep, s);
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < 6; k++) out[k] = ep[k];
+        ((int*)out)[6] = best;
     }
-    for (int k = 0; k < 6; k++) {
-        const double v = block_reduce_1024<double>(acc[k], s, false);
-        if (threadIdx.x == 0) out[k] = (float)v;
-    }
-    // first arg-max (strict >, main.cpp:348-353)
-    __shared__ float sv[1024];
-    __shared__ int si[1024];
-    sv[threadIdx.x] = bw;
-    si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const float ov = sv[threadIdx.x + o];
-            const int oi = si[threadIdx.x + o];
-            if (ov > sv[threadIdx.x] || (ov == sv[threadIdx.x] && oi < si[threadIdx.x])) {
-                sv[threadIdx.x] = ov;
-                si[threadIdx.x] = oi;
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) ((int*)out)[6] = si[0];
 }
 
 /* Per-particle PHD cardinality Σ_j w_j (double sum); one wave per particle. */
@@ -4207,13 +4011,9 @@ __global__ void __launch_bounds__(256)
     const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (p >= n) return;
     const int lane = threadIdx.x & 63;
-    const int sref = src[p];
-    const bool in_x = (sref & PHD_SLAB_X) != 0;
-    const int sl = sref & PHD_SLAB_MASK;
-    const float* w = (in_x ? map_x : map_in) + (size_t)sl * NF * cap;
-    const int sz = in_x ? size_x[sl] : size_in[sl];
+    const Slab m = slab_of(src[p], map_in, size_in, map_x, size_x, cap);
     double s = 0.0;
-    for (int k = lane; k < sz; k += 64) s += (double)w[k];
+    for (int k = lane; k < m.size; k += 64) s += (double)m.map[k];
     s = wave_sum_d(s);
     if (lane == 0) cn[p] = (float)s;
 }

@@ -7,9 +7,9 @@
  * Two stages, both enqueued after the update and before the step's resample
  * (which rewrites the poses, the log-weights and the slab references):
  *   stage 1  k_trace_weights   one 1024-thread workgroup: its own log-sum-exp
- *            of the un-normalised log-weights (normalize_block's order), nEff
- *            and the decision, the expected pose and the first arg-max in
- *            k_expected_pose's order; leaves the normalised weights and the
+ *            of the un-normalised log-weights, nEff and the decision, the
+ *            expected pose and the first arg-max, by k_normalize's and
+ *            k_expected_pose's block functions; leaves the normalised weights and the
  *            arg-max particle's slab reference for stage 2
  *   stage 2  k_trace_card      one workgroup per TRACE_PB particles: Σ_j w_j of
  *            each map by one wave (k_cardinality's sum), weighted partials
@@ -19,73 +19,30 @@
  */
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
-#include <climits>
 #include <cstdint>
 
+#include "phd_block.h"
 #include "phd_device.h"
 #include "phd_devutil.h"
 #include "phd_kernels.h"
+#include "phd_slab.h"
 #include "phd_trace.h"
 
 namespace phd {
-
-#define NF 7 /* fields per component (SoA rows: weight, mean x/y, cov 0..3) */
-
-/* chunk_sum_block's order (phd_kernels.hip): chunks of 1024 entries, each a
- * wave scan and the 16 wave totals in order, the chunk totals in order */
-template <class F>
-__device__ __forceinline__ double trace_chunk_sum(int n, F&& f, double* s /* 32 doubles */) {
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-    double total = 0.0;
-    for (int c = 0; c * RS_THREADS < n; c++) {
-        const int i = c * RS_THREADS + t;
-        double x = i < n ? f(i) : 0.0;
-        x = wave_incl_scan_d(x);
-        double* sb = s + (c & 1) * 16;
-        if (lane == 63) sb[wid] = x;
-        __syncthreads();
-        double cs = 0.0;
-#pragma unroll
-        for (int w = 0; w < RS_THREADS / 64; w++) cs += sb[w];
-        total += cs;
-    }
-    return total;
-}
-
-/* k_expected_pose's block sum: xor butterfly per wave, the wave totals in order */
-__device__ __forceinline__ double trace_block_sum(double v, double* s) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0) s[wid] = v;
-    __syncthreads();
-    double r = 0.0;
-    for (int w = 0; w < RS_THREADS / 64; w++) r += s[w];
-    __syncthreads();
-    return r;
-}
 
 __global__ void __launch_bounds__(RS_THREADS) k_trace_weights(TraceArgs a) {
     __shared__ double s_d[64];
     __shared__ double s_r[32];
     __shared__ float s_f[32];
-    __shared__ float sv[RS_THREADS];
-    __shared__ int si[RS_THREADS];
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+    const int t = threadIdx.x;
     const int n = a.n;
-    // log-sum-exp, nEff and the decision: normalize_block's arithmetic
+    // log-sum-exp, nEff and the decision: normalize_block's arithmetic (w_norm beside logw)
     float mx = -INFINITY;
     for (int i = t; i < n; i += RS_THREADS) mx = fmaxf(mx, a.logw[i]);
-    mx = wave_incl_max(mx);
-    if (lane == 63) s_f[wid] = mx;
-    __syncthreads();
-    mx = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < RS_THREADS / 64; w++) mx = fmaxf(mx, s_f[w]);
-    const double sum = trace_chunk_sum(n, [&](int i) { return (double)expf(a.logw[i] - mx); }, s_d);
+    PHD_BLOCK_MAX_1024(mx, s_f, t & 63, t >> 6);
+    const double sum = chunk_sum_block(n, [&](int i) { return (double)expf(a.logw[i] - mx); }, s_d);
     const float lse = d_safe_log((float)sum) + mx;
-    const double s2 = trace_chunk_sum(
+    const double s2 = chunk_sum_block(
         n,
         [&](int i) {
             const float w = a.logw[i] - lse;
@@ -93,41 +50,14 @@ __global__ void __launch_bounds__(RS_THREADS) k_trace_weights(TraceArgs a) {
             return (double)expf(2 * w);
         },
         s_d + 32);
-    const float neff = (float)(1.0 / (double)(float)s2 / (double)n);
-    const int resample = (a.has_meas == 2 || (a.has_meas && neff <= a.resample_thresh)) ? 1 : 0;
-    // expected pose and first arg-max: k_expected_pose's order on the normalised weights
-    double acc[6] = {0, 0, 0, 0, 0, 0};
-    float bw = -FLT_MAX;
-    int bi = INT_MAX;
-    for (int i = t; i < n; i += RS_THREADS) {
-        const float w = a.logw[i] - lse;
-        const float ew = expf(w);
-        const float* ps = (const float*)&a.pose[i];
-        for (int k = 0; k < 6; k++) acc[k] += (double)(ew * ps[k]);
-        if (w > bw) {
-            bw = w;
-            bi = i;
-        }
-    }
+    const float neff = neff_of(s2, n);
+    const int resample = resample_decision(neff, a.has_meas, a.resample_thresh);
+    // expected pose and first arg-max: k_expected_pose's routine on the normalised weights
     float ep[6];
-    for (int k = 0; k < 6; k++) ep[k] = (float)trace_block_sum(acc[k], s_r);
-    sv[t] = bw;
-    si[t] = bi;
-    __syncthreads();
-    for (int o = RS_THREADS / 2; o > 0; o >>= 1) {
-        if (t < o) {
-            const float ov = sv[t + o];
-            const int oi = si[t + o];
-            if (ov > sv[t] || (ov == sv[t] && oi < si[t])) {
-                sv[t] = ov;
-                si[t] = oi;
-            }
-        }
-        __syncthreads();
-    }
+    const int amax = expected_pose_block(n, [&](int i) { return a.logw[i] - lse; }, a.pose, ep, s_r);
     if (t == 0) {
         // (every weight NaN or below -FLT_MAX: no arg-max; particle 0 stands in)
-        const int best = si[0] >= 0 && si[0] < n ? si[0] : 0;
+        const int best = amax >= 0 && amax < n ? amax : 0;
         phd_trace_record r;
         r.step = a.step;
         r.n_live = n;
@@ -135,7 +65,7 @@ __global__ void __launch_bounds__(RS_THREADS) k_trace_weights(TraceArgs a) {
         r.resampled = resample;
         r.neff = neff;
         r.expected_pose = phd_pose{ep[0], ep[1], ep[2], ep[3], ep[4], ep[5]};
-        r.map_particle = si[0];
+        r.map_particle = amax;
         r.map_pose = a.pose[best];
         r.card_expected = 0.f;  // stage 2
         r.card_map = 0.f;
@@ -163,13 +93,10 @@ __global__ void __launch_bounds__(256) k_trace_card(TraceArgs a) {
         const int p = base + q;
         double term = 0.0;
         if (p < a.n) {
-            const int sref = a.src[p];
-            const bool in_x = (sref & PHD_SLAB_X) != 0;
-            const int sl = sref & PHD_SLAB_MASK;
-            const float* w = (in_x ? a.map_x : a.map_in) + (size_t)sl * NF * a.cap;
-            const int sz = min(max(in_x ? a.size_x[sl] : a.size_in[sl], 0), a.cap);
+            const Slab m = slab_of(a.src[p], a.map_in, a.size_in, a.map_x, a.size_x, a.cap);
+            const int sz = min(max(m.size, 0), a.cap);
             double s = 0.0;
-            for (int k = lane; k < sz; k += 64) s += (double)w[k];
+            for (int k = lane; k < sz; k += 64) s += (double)m.map[k];
             s = wave_sum_d(s);
             const float cn = (float)s;
             term = (double)expf(a.w_norm[p]) * (double)cn;
@@ -206,18 +133,15 @@ __global__ void __launch_bounds__(256) k_trace_finish(TraceArgs a, int nparts) {
         if (t == 0) a.rec->card_expected = (float)(((s_w[0] + s_w[1]) + s_w[2]) + s_w[3]);
     } else if (blockIdx.x == 1) {
         if (!a.snap) return;
-        const int sref = a.hand[TRACE_H_SLAB];
-        const bool in_x = (sref & PHD_SLAB_X) != 0;
-        const int sl = sref & PHD_SLAB_MASK;
-        const float* s = (in_x ? a.map_x : a.map_in) + (size_t)sl * NF * a.cap;
-        const int sz = min(max(in_x ? a.size_x[sl] : a.size_in[sl], 0), a.cap);
+        const Slab m = slab_of(a.hand[TRACE_H_SLAB], a.map_in, a.size_in, a.map_x, a.size_x, a.cap);
+        const int sz = min(max(m.size, 0), a.cap);
         const int rows = min(sz, a.snap_cap);
         float* o = (float*)a.snap;
         // Gaussian2D words: cov[0..3] (rows 3..6), mean[0..1] (rows 1..2), weight (row 0)
-        for (int e = t; e < a.snap_cap * NF; e += 256) {
-            const int k = e / NF, j = e - k * NF;
+        for (int e = t; e < a.snap_cap * PHD_NF; e += 256) {
+            const int k = e / PHD_NF, j = e - k * PHD_NF;
             const int f = j < 4 ? 3 + j : j < 6 ? j - 3 : 0;
-            o[e] = k < rows ? s[(size_t)f * a.cap + k] : 0.f;
+            o[e] = k < rows ? m.map[(size_t)f * a.cap + k] : 0.f;
         }
     } else {
         if (!a.card || !a.card_all) return;

@@ -1593,6 +1593,56 @@ def test_expected_pose_and_cardinality(gpu):
     f.close()
 
 
+@pytest.mark.parametrize("cid", [2, 3])
+def test_particle_records_round_trip(gpu, cid):
+    """phd_pack_particles -> phd_unpack_particles into a second context: poses,
+    log-weights, maps and (CPHD, config 3's model) the cardinality coefficients
+    arrive bit for bit.  n = 8, map capacity 16, maps of 0 .. 16 components
+    (empty and full slabs), a permuted source list that repeats one particle."""
+    import phdslam
+    import torch
+    n, cap = 8, 16
+    sizes = np.array([0, 1, 15, 16, 2, 8, 16, 0])
+    src_idx = np.array([3, 0, 7, 7, 1, 5, 2, 6], np.int32)
+    c, poses, lw, maps, offs, z = phdslam.config_scenario(cid, n=n, G=cap, M=4)
+    keep = np.concatenate([np.arange(offs[p], offs[p] + sizes[p]) for p in range(n)]).astype(np.int64)
+    maps, offs = maps[keep], np.concatenate([[0], np.cumsum(sizes)]).astype(offs.dtype)
+    lw = np.random.default_rng(3).normal(-8, 3, n).astype(np.float32)
+    cphd = c.filterType == 1
+    caps = dict(map_capacity=cap, max_measurements=8, candidate_capacity=128, survivor_capacity=64)
+    fs = []
+    for k in range(2):  # source, destination (other poses and weights: everything must be overwritten)
+        f = _filter(c, n, **caps)
+        f.load(poses if k == 0 else poses[::-1].copy(), lw if k == 0 else lw[::-1].copy(), maps, offs)
+        if cphd:  # a CPHD update leaves cardinality coefficients to carry (and to read back)
+            f.set_step_births(0)
+            f.set_check_each_update(False)
+            f.set_measurements(z)
+            f.predict_update(None, 0, do_predict=False)
+        fs.append(f)
+    a, b = fs
+    dev = torch.device("cuda", 0)
+    rec = torch.zeros(n * a.record_bytes(), dtype=torch.uint8, device=dev)
+    a.pack(torch.from_numpy(src_idx).to(dev).data_ptr(), n, rec.data_ptr())
+    torch.cuda.synchronize()  # (the two contexts run on their own streams)
+    dst_idx = torch.arange(n, dtype=torch.int32, device=dev)
+    b.unpack(rec.data_ptr(), dst_idx.data_ptr(), n)
+    ap, aw, am, ao = a.export()
+    bp, bw, bm, bo = b.export()
+    assert bp.tobytes() == ap[src_idx].tobytes() and bw.tobytes() == aw[src_idx].tobytes()
+    np.testing.assert_array_equal(np.diff(bo), np.diff(ao)[src_idx])
+    if not cphd:
+        np.testing.assert_array_equal(np.diff(ao), sizes)
+    # (CPHD: the sizes after the update) an empty and a full slab both travel
+    assert 0 in np.diff(ao)[src_idx] and cap in np.diff(ao)[src_idx], np.diff(ao)
+    for j, p in enumerate(src_idx):
+        assert bm[bo[j]:bo[j + 1]].tobytes() == am[ao[p]:ao[p + 1]].tobytes(), (j, p)
+    if cphd:
+        assert b.cardinality_distribution().tobytes() == a.cardinality_distribution()[src_idx].tobytes()
+    a.close()
+    b.close()
+
+
 @pytest.mark.parametrize("scans", [1135])
 def test_multistep_sequence_config1_data(gpu, scans):
     """Config 1 (BASELINE configs[0]) as the reference's loop runs it

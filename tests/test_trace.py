@@ -205,6 +205,53 @@ def test_records_equal_twin(gpu, cid, n, map_estimate):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 63, 65, 1023, 1025, 2049])
+def test_reductions_equal_synchronous_calls(gpu, n):
+    """The block reductions the trace shares with the synchronous kernels, at one
+    lane, a wave edge, a chunk edge (1024) and a third chunk: one scan (map
+    capacity 8, 4 measurements) from spread log-weights; the record's nEff,
+    decision, expected pose and arg-max equal phd_normalize / phd_neff /
+    phd_expected_pose bit for bit.  phd_lse_parts' (max, Σ exp) give the same
+    log-sum-exp: phd_normalize's is not returned, so the weights normalised by
+    log(Σ) + max are held against phd_normalize's at the tolerance
+    test_normalize_neff_resample_bit_exact uses for that comparison."""
+    import parity
+    import phdslam
+    c, poses, lw, maps, offs, z = _scenario(2, n, G=2, M=M)
+    lw = np.random.default_rng(n).normal(-8, 3, n).astype(np.float32)
+    run = []
+    for traced in (False, True):
+        f = phdslam.PHDFilter(n, c, map_capacity=8, max_measurements=8, candidate_capacity=128, survivor_capacity=64)
+        f.set_seed(4242)
+        if _split(2, n):
+            f.set_update_form(2)
+        f.set_check_each_update(False)
+        f.load(poses, lw, maps, offs)
+        f.set_measurements(z)
+        run.append(f)
+    t, f = run
+    t.predict_update(_control(c), 0, do_predict=False)
+    w_un = t.export(with_maps=False)[1]
+    mx, sm = t.lse_parts()
+    t.normalize()
+    neff = np.float32(t.neff())
+    pose, mi = t.expected_pose()
+    tp, wn = t.export(with_maps=False)[:2]
+    f.enable_trace(1)
+    assert f.step(_control(c), do_predict=False, step=0, readback=False) is None
+    r = f.read_trace()[0]
+    t.close()
+    f.close()
+    assert _bits(np.float32(r["neff"])) == _bits(neff)
+    assert bool(r["resampled"]) == bool(neff <= c.resampleThresh)
+    assert r["map_particle"] == mi
+    assert _bits(r["expected_pose"]) == _bits(pose)
+    assert _bits(r["map_pose"]) == _bits(tp[mi])
+    lse = np.float32(np.log(np.float32(sm))) + np.float32(mx)
+    assert parity.close(wn, w_un - lse, 1e-5, floor=1e-5).all()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("snap", [64, 4])
 def test_map_snapshot(gpu, snap):
     scans, _ = _twin_run(2, 300, 0)
