@@ -95,6 +95,7 @@ struct phd_ctx {
     int upd_threads_req = 0; // 0 = automatic (choose_update_threads)
     int upd_resident = 0;    // update workgroups resident at once on the device
     int upd_resident_a = 0;  // the same for part A of the three-launch CPHD update
+    int upd_metric = 0;      // the merge distance the launch was sized for (its kernels' registers)
     int upd_resident_p = 0;  // the same for the launch that carries a fused predict (its own registers)
     int epool = 0;
     int upd_cphd = 0;            // launch configured for the CPHD kernels
@@ -454,7 +455,16 @@ __global__ void k_iota(int* a, int n) {
 /* The workgroup update kernel of nt threads: part 0 the fused PHD update,
  * 1 / 2 part A / part C of the split update (CPHD: always split, with
  * k_cphd_terms between the parts; PHD: split when it pays, update_form). */
-static const void* update_kernel(int nt, int cphd, int part) {
+static const void* update_kernel(int nt, int cphd, int part, int metric = 0) {
+    const int ti = nt == 256 ? 0 : nt == 512 ? 1 : 2;
+    if (metric == 1 && part != 1) {  // the launches that hold the merge (parts A have none)
+        const void* h[3][3] = {
+            {(const void*)k_update_fused_256_h, (const void*)k_update_fused_512_h, (const void*)k_update_fused_1024_h},
+            {(const void*)k_update_phd_c_256_h, (const void*)k_update_phd_c_512_h, (const void*)k_update_phd_c_1024_h},
+            {(const void*)k_update_cphd_c_256_h, (const void*)k_update_cphd_c_512_h,
+             (const void*)k_update_cphd_c_1024_h}};
+        return cphd ? (part == 2 ? h[2][ti] : nullptr) : h[part == 2 ? 1 : 0][ti];
+    }
     const void* k[2][3][3] = {
         {{(const void*)k_update_fused_256, (const void*)k_update_fused_512, (const void*)k_update_fused_1024},
          {(const void*)k_update_phd_a_256, (const void*)k_update_phd_a_512, (const void*)k_update_phd_a_1024},
@@ -493,6 +503,8 @@ static int blocks_per_cu(const void* kernel, int nt, size_t lds) {
 static int configure_update_launch(phd_ctx* c, int req) {
     const phd_capacity& cap = c->cap;
     const int cphd = c->cfg_set && c->cfg.filterType == PHD_FILTER_CPHD ? 1 : 0;
+    // the kernels that hold the merge differ by metric (registers, hence residency)
+    const int metric = c->cfg_set && c->cfg.distanceMetric == 1 ? 1 : 0;
     int ncu = 0;
     hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
     if (ncu <= 0) ncu = 1;
@@ -512,7 +524,7 @@ static int configure_update_launch(phd_ctx* c, int req) {
                                       cap.survivor_capacity, e, nt, cphd, pc)
                     .total;
             };
-            const void* kc = update_kernel(nt, cphd, pc);
+            const void* kc = update_kernel(nt, cphd, pc, metric);
             // minimal edge pool: one edge per candidate (+16 for CPHD): the births
             // join the detected landmarks' clusters — config 4's shard overflowed a
             // pool of K / 2 + 32 in 48 % of its particle-updates (serial greedy), and
@@ -562,6 +574,7 @@ static int configure_update_launch(phd_ctx* c, int req) {
     }
     c->upd_threads = best;
     c->upd_cphd = cphd;
+    c->upd_metric = metric;
     c->upd_split = best_split;
     c->upd_threads_req = req;
     c->upd_lds = best_lds;
@@ -583,7 +596,8 @@ static int configure_update_launch(phd_ctx* c, int req) {
             kp = best == 256 ? (const void*)k_update_cphd_a_p256 : (const void*)k_update_cphd_a_p512;
             lp = c->upd_lds_a;
         } else if (!cphd && !best_split && best <= 512) {
-            kp = best == 256 ? (const void*)k_update_fused_p256 : (const void*)k_update_fused_p512;
+            kp = metric ? (best == 256 ? (const void*)k_update_fused_p256_h : (const void*)k_update_fused_p512_h)
+                        : (best == 256 ? (const void*)k_update_fused_p256 : (const void*)k_update_fused_p512);
             lp = c->upd_lds;
         }
         c->upd_resident_p = kp ? blocks_per_cu(kp, best, lp) * ncu : 0;
@@ -678,8 +692,11 @@ int phd_ctx_create(phd_ctx** out, int device, int n_particles, const phd_capacit
     for (int nt = UPD_THREADS_MIN; nt <= UPD_THREADS_MAX; nt *= 2)
         for (int cp = 0; cp < 2; cp++)
             for (int part = cp; part < 3; part++)
-                hipFuncSetAttribute(update_kernel(nt, cp, part), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024);
+                for (int metric = 0; metric < (part == 1 ? 1 : 2); metric++)
+                    hipFuncSetAttribute(update_kernel(nt, cp, part, metric),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipFuncSetAttribute((const void*)k_update_fused_p256_h, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipFuncSetAttribute((const void*)k_update_fused_p512_h, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)k_update_cphd_a_p256, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)k_update_cphd_a_p512, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)k_update_fused_p256, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -717,8 +734,10 @@ int phd_set_config(phd_ctx* ctx, const phd_slam_config* cfg) {
     ctx->cfg = *cfg;
     ctx->cfg_set = true;
     const int cphd = cfg->filterType == PHD_FILTER_CPHD ? 1 : 0;
-    if (cphd != ctx->upd_cphd) {
-        // the CPHD kernels have their own LDS layout and occupancy
+    const int metric = cfg->distanceMetric == 1 ? 1 : 0;
+    if (cphd != ctx->upd_cphd || metric != ctx->upd_metric) {
+        // the CPHD kernels have their own LDS layout and occupancy, the
+        // Hellinger kernels their own registers
         if (set_device(ctx)) return PHD_E_HIP;
         int rc = configure_update_launch(ctx, ctx->upd_threads_req);
         if (rc) return rc;
@@ -1254,7 +1273,11 @@ static int launch_update_mixed(phd_ctx* ctx) {
     if (!ctx->dyn) return fail(PHD_E_ARG, "feature_model 2 needs phd_enable_dynamic");
     if (cfg.filterType != PHD_FILTER_PHD) return fail(PHD_E_UNSUPPORTED, "feature_model 2 with the CPHD filter");
     if (cfg.particleWeighting != 0) return fail(PHD_E_UNSUPPORTED, "particle_weighting != 0 is not implemented");
-    if (cfg.distanceMetric != 0) return fail(PHD_E_UNSUPPORTED, "distance_metric != 0 (Hellinger) is not implemented");
+    if (cfg.distanceMetric == 1)
+        return fail(PHD_E_UNSUPPORTED,
+                    "feature_model 2 with distance_metric 1: the reference's Hellinger distance of 4-D components is "
+                    "the constant 0 (device_math.cuh:366-371), which would merge every dynamic component into one");
+    if (cfg.distanceMetric != 0) return fail(PHD_E_UNSUPPORTED, "distance_metric must be 0 (Mahalanobis)");
     if (ctx->replay) return fail(PHD_E_UNSUPPORTED, "feature_model 2 in replay mode");
     if (ctx->d_map_x) return fail(PHD_E_UNSUPPORTED, "feature_model 2 with migrated (sharded) particles");
     if (ctx->n <= 0) return PHD_OK;
@@ -1342,7 +1365,9 @@ static int launch_update(phd_ctx* ctx, const FusedPredict* fused = nullptr, cons
     if (cfg.featureModel != PHD_FEATURE_STATIC)
         return fail(PHD_E_UNSUPPORTED,
                     "feature_model 1 (dynamic only): the reference's update is a stub (phdfilter.cu:3663-3671)");
-    if (cfg.distanceMetric != 0) return fail(PHD_E_UNSUPPORTED, "distance_metric != 0 (Hellinger) is not implemented");
+    if (cfg.distanceMetric != 0 && cfg.distanceMetric != 1)
+        return fail(PHD_E_UNSUPPORTED, "distance_metric must be 0 (Mahalanobis) or 1 (Hellinger)");
+    const int metric = cfg.distanceMetric;  // the merge's distance: selects the kernels that hold the merge
     const bool cphd = cfg.filterType == PHD_FILTER_CPHD;
     if (cfg.filterType != PHD_FILTER_PHD && !cphd) return fail(PHD_E_UNSUPPORTED, "unknown filter_type");
     if (cphd) {
@@ -1370,6 +1395,10 @@ static int launch_update(phd_ctx* ctx, const FusedPredict* fused = nullptr, cons
     }
     if (cfg.particleWeighting != 0)
         return fail(PHD_E_UNSUPPORTED, "particle_weighting != 0 is not implemented on the device path");
+    if (ctx->upd_metric != metric) {  // the launch was sized for the other metric's kernels
+        int rc = configure_update_launch(ctx, ctx->upd_threads_req);
+        if (rc) return rc;
+    }
     const int in_set = ctx->replay ? 0 : (slots ? ctx->cur ^ 1 : ctx->cur);
     const int out_set = in_set ^ 1;
     const int grid = slots ? nslots : ctx->n;
@@ -1510,7 +1539,7 @@ static int launch_update(phd_ctx* ctx, const FusedPredict* fused = nullptr, cons
             }
             const int lead = rs_lead(a);
             rs_beside(st);
-            hipLaunchKernelGGL((void (*)(UpdateArgs))update_kernel(ctx->upd_threads, 1, 2), dim3(grid + lead),
+            hipLaunchKernelGGL((void (*)(UpdateArgs))update_kernel(ctx->upd_threads, 1, 2, metric), dim3(grid + lead),
                                dim3(ctx->upd_threads), ctx->upd_lds, st, a);
             ctx->cn_valid = true;
         } else if (ctx->upd_split) {
@@ -1535,8 +1564,13 @@ static int launch_update(phd_ctx* ctx, const FusedPredict* fused = nullptr, cons
             a.pose_prior = nullptr;
             a.logw_prior = nullptr;
             a.order = 1;  // last-written first, XCD-preserving (upd_particle)
-            hipLaunchKernelGGL((void (*)(UpdateArgs))update_kernel(ctx->upd_threads, 0, 2), dim3(grid + lead),
+            hipLaunchKernelGGL((void (*)(UpdateArgs))update_kernel(ctx->upd_threads, 0, 2, metric), dim3(grid + lead),
                                dim3(ctx->upd_threads), ctx->upd_lds, st, a);
+        } else if (metric == 1) {
+            const void* kh = fused && ctx->upd_threads == 256   ? (const void*)k_update_fused_p256_h
+                             : fused && ctx->upd_threads == 512 ? (const void*)k_update_fused_p512_h
+                                                                : update_kernel(ctx->upd_threads, 0, 0, 1);
+            hipLaunchKernelGGL((void (*)(UpdateArgs))kh, dim3(grid), dim3(ctx->upd_threads), ctx->upd_lds, st, a);
         } else if (fused && ctx->upd_threads == 256) {
             hipLaunchKernelGGL(k_update_fused_p256, dim3(grid), dim3(256), ctx->upd_lds, st, a);
         } else if (fused && ctx->upd_threads == 512) {

@@ -167,6 +167,42 @@ __device__ __forceinline__ float d_mahal(float ax, float ay, float a0, float a1,
     return d0 * d0 * i0 + d0 * d1 * (i1 + i2) + d1 * d1 * i3;
 }
 
+/* computeHellingerDist for 2-D Gaussians (device_math.cuh:373-413), a the
+ * first argument (the merge's seed).  Evaluation order, every step one float
+ * operation unless noted (the tests' numpy restatement takes the same steps):
+ *   i = a.mean - b.mean;  s_k = a_k + b_k;  det = s0 s3 - s2 s1
+ *   (v0, v1, v2, v3) = (s3, -s1, -s2, s0) / det when det > FLT_MIN, else the identity
+ *   q = i0 i0 v0 + i0 i1 (v1 + v2) + i1 i1 v3        (left to right)
+ *   eps = (float)(-0.25 (double)q)
+ *   n = 1 / (det / 4)
+ *   p = a b entry by entry as the reference writes it:
+ *       p0 = a0 b0 + a2 b1, p1 = a1 b0 + a3 b1, p2 = a0 b2 + a2 b3, p3 = a1 b2 + a3 b3
+ *   c = n sqrt(p0 p3 - p2 p1);  d = 1 - sqrt(c) exp(eps)
+ * with the shared deterministic exp (phd_detmath.h).  NOT symmetric: p is a b,
+ * and the entries of b a round differently, so d(a, b) and d(b, a) can differ
+ * in the last bits — the merges always pass the higher-priority candidate
+ * first, as the greedy passes its seed.  A negative p0 p3 - p2 p1 (rounding,
+ * ill-conditioned covariances) gives NaN: no merge, on every path alike. */
+__device__ __forceinline__ float d_hellinger(float ax, float ay, float a0, float a1, float a2, float a3, float bx,
+                                             float by, float b0, float b1, float b2, float b3) {
+    const float i0 = ax - bx, i1 = ay - by;
+    const float s0 = a0 + b0, s1 = a1 + b1, s2 = a2 + b2, s3 = a3 + b3;
+    const float det = s0 * s3 - s2 * s1;
+    float v0 = 1.f, v1 = 0.f, v2 = 0.f, v3 = 1.f;
+    if (det > FLT_MIN) {
+        v0 = s3 / det;
+        v1 = -s1 / det;
+        v2 = -s2 / det;
+        v3 = s0 / det;
+    }
+    const float q = i0 * i0 * v0 + i0 * i1 * (v1 + v2) + i1 * i1 * v3;
+    const float eps = (float)(-0.25 * (double)q);
+    const float n = 1.0f / (det / 4);
+    const float p0 = a0 * b0 + a2 * b1, p1 = a1 * b0 + a3 * b1, p2 = a0 * b2 + a2 * b3, p3 = a1 * b2 + a3 * b3;
+    const float c = n * sqrtf(p0 * p3 - p2 * p1);
+    return 1 - sqrtf(c) * phd_det_expf(eps);
+}
+
 /* Wave64 helpers. */
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -234,13 +234,64 @@ __device__ __forceinline__ float cand_mahal(const float4& pa, const float4& va, 
     return d_mahal(pa.x, pa.y, va.x, va.y, va.z, va.w, pb.x, pb.y, vb.x, vb.y, vb.z, vb.w);
 }
 
+__device__ __forceinline__ float cand_hellinger(const float4& pa, const float4& va, const float4& pb,
+                                                const float4& vb) {
+    return d_hellinger(pa.x, pa.y, va.x, va.y, va.z, va.w, pb.x, pb.y, vb.x, vb.y, vb.z, vb.w);
+}
+
+/* The merge distance of config key distance_metric (phdfilter.cu:2802-2805):
+ * 0 Mahalanobis, 1 Hellinger.  a is the seed — the candidate of higher merge
+ * priority: the Hellinger distance depends on the order in its last bits
+ * (d_hellinger), the Mahalanobis distance does not.  The serial and the
+ * parallel merge both decide through this one function. */
+template <int METRIC>
+__device__ __forceinline__ constexpr bool metric_hellinger() {
+    return METRIC == 1;
+}
+
+template <int METRIC>
+__device__ __forceinline__ float cand_dist(const float4& pa, const float4& va, const float4& pb, const float4& vb) {
+    if constexpr (METRIC == 0)
+        return cand_mahal(pa, va, pb, vb);
+    else
+        return metric_hellinger<METRIC>() ? cand_hellinger(pa, va, pb, vb) : cand_mahal(pa, va, pb, vb);
+}
+
+/* The Mahalanobis-form threshold the merge's culls work with: every pair with
+ * cand_dist < T has dmu' ((A + B) / 2)^-1 dmu < merge_cull_T (before the
+ * culls' own 5 % margin).  Metric 0: T itself.  Metric 1 (derivation above
+ * merge_parallel): T_M = -8 ln(1 - (T + PHD_HELL_SLACK)); +inf when that
+ * argument is not positive (T >= 1 - slack), NaN for a NaN T — both send the
+ * particle to the serial greedy. */
+#define PHD_HELL_SLACK 4e-3f
+/* the binned ("well-conditioned") class under metric 1: lambda_min > lambda_max / 100 */
+#define PHD_HELL_COND 1e-2f
+/* T_M above this: the lattice cell spans 8 standard deviations and the cull
+ * removes next to nothing — the serial greedy takes the particle */
+#define PHD_HELL_TM_MAX 64.f
+template <int METRIC>
+__device__ __forceinline__ float merge_cull_T(float T) {
+    if (METRIC != 0 && metric_hellinger<METRIC>()) {
+        const float r = 1.f - (T + PHD_HELL_SLACK);
+        if (!(r > 0.f)) return r == r ? INFINITY : r;
+        return -8.f * phd_det_logf(r);
+    } else {
+        return T;
+    }
+}
+
 /* cand_mahal(p, v, p, v) < T, bit for bit, for a finite mean: the differences
  * are exact zeros, so the distance is (0 i0 + 0 (i1 + i2)) + 0 i3 — zero when the
  * three inverse terms are finite, NaN otherwise.  They are certainly finite
  * when every |v| <= 1e18 (the halved sums are then v itself and the products
  * finite) and |det| >= 1e-19 (1 / det <= 1e19, every inverse term <= 1e37);
- * only the rest evaluates the distance. */
+ * only the rest evaluates the distance.
+ * Metric 1: no shortcut, the Hellinger own-distance itself (1 - sqrt(c) with
+ * c = 4 sqrt(det(v v)) / det(2 v) near 1: a few ulps either side of 0, NaN when
+ * rounding turns det(v v) negative). */
+template <int METRIC = 0>
 __device__ __forceinline__ bool own_distance_below(const float4& p, const float4& v, float T) {
+    if (METRIC != 0 && metric_hellinger<METRIC>()) return cand_hellinger(p, v, p, v) < T;
     const float m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
     const float det = v.x * v.w - v.z * v.y;
     if (m <= 1e18f && fabsf(det) >= 1e-19f) return 0.f < T;
@@ -255,7 +306,11 @@ __device__ __forceinline__ bool own_distance_below(const float4& p, const float4
  * cull stays conservative; the lattice is sized by the exact maximum.  `bad`
  * flags what only the serial greedy reproduces: non-finite values or a failed
  * own-distance test d(i,i) < T; lmax tracks the largest well-conditioned
- * lambda_max. */
+ * lambda_max.  Metric 1 bins a narrower class (lambda_min > 1e-2 lambda_max):
+ * the float Hellinger distance of two such candidates is within PHD_HELL_SLACK
+ * of the exact one (merge_parallel), beyond it the product's determinant
+ * cancels and only the exact all-pairs pass of the wild tail is safe. */
+template <int METRIC = 0>
 __device__ __forceinline__ float4 cand_record(float x, float y, float w, const float4& v, float T, int& bad,
                                               float& lmax, unsigned tag) {
     float4 p = make_float4(x, y, w, 0.f);
@@ -264,8 +319,8 @@ __device__ __forceinline__ float4 cand_record(float x, float y, float w, const f
     const float rt = sqrtf(h * h + b * b);
     const float l1 = 0.5f * (aa + d) + rt, l2 = 0.5f * (aa + d) - rt;
     const bool finite = (w > 0.f) && (w < INFINITY) && (fabsf(x) < INFINITY) && (fabsf(y) < INFINITY);
-    const bool ok = finite && (l1 < INFINITY) && l2 > 1e-4f * l1;
-    bad |= !finite || !own_distance_below(p, v, T);  // the greedy's own-distance test
+    const bool ok = finite && (l1 < INFINITY) && l2 > (METRIC != 0 && metric_hellinger<METRIC>() ? PHD_HELL_COND : 1e-4f) * l1;
+    bad |= !finite || !own_distance_below<METRIC>(p, v, T);  // the greedy's own-distance test
     if (ok) lmax = fmaxf(lmax, l1);
     const unsigned lb = __float_as_uint(ok ? fmaxf(l1, 1e-30f) * 1.015625f : -1.f);
     p.w = __uint_as_float((lb & 0xffff0000u) | tag);

@@ -407,6 +407,21 @@ __global__ void k_cphd_cardinality(const int* src, const double* cn_coef, const 
                                    const double* lfact, int Nmax, int n, float* out);
 __global__ void k_update_fused_p256(UpdateArgs a);
 __global__ void k_update_fused_p512(UpdateArgs a);
+/* distance_metric 1 (Hellinger): the launches that hold the merge — the fused
+ * PHD update and both part C forms — instantiated a second time with the
+ * metric as a template parameter; parts A and the CPHD terms have no merge and
+ * serve both metrics */
+__global__ void k_update_fused_256_h(UpdateArgs a);
+__global__ void k_update_fused_512_h(UpdateArgs a);
+__global__ void k_update_fused_1024_h(UpdateArgs a);
+__global__ void k_update_fused_p256_h(UpdateArgs a);
+__global__ void k_update_fused_p512_h(UpdateArgs a);
+__global__ void k_update_phd_c_256_h(UpdateArgs a);
+__global__ void k_update_phd_c_512_h(UpdateArgs a);
+__global__ void k_update_phd_c_1024_h(UpdateArgs a);
+__global__ void k_update_cphd_c_256_h(UpdateArgs a);
+__global__ void k_update_cphd_c_512_h(UpdateArgs a);
+__global__ void k_update_cphd_c_1024_h(UpdateArgs a);
 __global__ void k_normalize(float* logw, int n, const float* lse_override, float* out, float resample_thresh,
                             int has_meas);
 __global__ void k_lse_parts(const float* logw, int n, float* out);

@@ -293,8 +293,9 @@ __device__ __forceinline__ void emit_merged(G1 float* dst, int cap, int slot, fl
  * iteration with block-parallel scans.  Exact fallback for particles the
  * parallel merge declines (non-finite candidates, edge-pool overflow).
  * key[i] is the candidate index of record i (NULL = identity) for the
- * lowest-index tie-break.  Outputs in selection order.  Returns nout. */
-template <int NT>
+ * lowest-index tie-break.  Outputs in selection order.  Returns nout.
+ * METRIC: the merge distance (cand_dist), the seed its first argument. */
+template <int NT, int METRIC = 0>
 __device__ int merge_serial(const Cand& C, const unsigned short* key, int ncand, short* cflag, float T, G1 float* dst,
                             int cap, double* s_red, float* s_redf) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -351,7 +352,7 @@ __device__ int merge_serial(const Cand& C, const unsigned short* key, int ncand,
         for (int i = tid; i < ncand; i += NT) {
             if (cflag[i] != 0) continue;
             const float4 p = C.P[i];
-            if (cand_mahal(bp, bv, p, C.V(i)) < T) {
+            if (cand_dist<METRIC>(bp, bv, p, C.V(i)) < T) {  // (the seed first)
                 cflag[i] = 2;
                 acc[0] += (double)p.z;
                 acc[1] += (double)(p.z * p.x);
@@ -535,7 +536,7 @@ __device__ __forceinline__ void merge_walk(const MergeScratch& X, int K, int Knw
 #ifndef PHD_WALK_UNROLL
 #define PHD_WALK_UNROLL 4
 #endif
-template <int WU, bool EXACT = false, bool SEG4 = false>
+template <int WU, bool EXACT = false, bool SEG4 = false, int METRIC = 0>
 __device__ __forceinline__ void walk_dealt(const MergeScratch& X, int qb, float px, float py, float tpw, int la, int na,
                                            int lb, int nb, float thr, int* npair, int plcap, int lc = 0, int nc = 0,
                                            int ld = 0, int nd = 0) {
@@ -592,7 +593,14 @@ __device__ __forceinline__ void walk_dealt(const MergeScratch& X, int qb, float 
 #pragma unroll
             for (int k = 0; k < WU; k++) {
                 const float4 vk = X.K.Vp(pp[k]);
-                const int ok = (int)(t0 + k < on) & (int)(cand_mahal(po, vo, pp[k], vk) < thr);
+                // (metric 1: the weights that order the pair are not at hand here, so
+                // either order lists it; M3b decides with the seed first)
+                int ok;
+                if (METRIC != 0 && metric_hellinger<METRIC>())
+                    ok = (int)(t0 + k < on) & (int)((cand_dist<METRIC>(po, vo, pp[k], vk) < thr) |
+                                                    (cand_dist<METRIC>(pp[k], vk, po, vo) < thr));
+                else
+                    ok = (int)(t0 + k < on) & (int)(cand_mahal(po, vo, pp[k], vk) < thr);
                 m |= ok << k;
             }
         } else {
@@ -630,7 +638,7 @@ __device__ __forceinline__ void walk_dealt(const MergeScratch& X, int qb, float 
     }
 }
 
-template <int NT, int WU = PHD_WALK_UNROLL>
+template <int NT, int METRIC = 0, int WU = PHD_WALK_UNROLL>
 __device__ __forceinline__ void merge_walk_cell(const MergeScratch& X, int K, int Knw, int Px, int Py, int lgPx,
                                                 float invR, float thr, float T, int* npair, int plcap) {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -687,8 +695,8 @@ __device__ __forceinline__ void merge_walk_cell(const MergeScratch& X, int K, in
         // every such pair (a few wild births at close range would overflow the
         // pair list: 7 % of the particle-updates of bench.py --mode sequence)
         if (Knw < K)
-            walk_dealt<1, true>(X, qb, p.x, p.y, p.w, wild ? q + 1 : Knw, !live ? 0 : wild ? K - q - 1 : K - Knw, 0, 0,
-                                T, npair, plcap);
+            walk_dealt<1, true, false, METRIC>(X, qb, p.x, p.y, p.w, wild ? q + 1 : Knw,
+                                               !live ? 0 : wild ? K - q - 1 : K - Knw, 0, 0, T, npair, plcap);
     }
 }
 
@@ -771,8 +779,44 @@ __device__ __forceinline__ bool cluster_moments(const MergeScratch& X, int i, in
  * Returns nout (outputs in candidate-index order of their seeds), or -1 when
  * the particle needs the serial greedy (non-finite candidate, d(i,i) >= T,
  * edge-pool overflow).
+ *
+ * METRIC 1 (Hellinger, d_hellinger) has neither property the above rests on,
+ * and both are re-established:
+ *
+ * Directed edges.  d(a, b) and d(b, a) differ in their last bits when a
+ * covariance is not exactly symmetric (the entries of a b and b a then round
+ * differently).  The greedy only ever evaluates d(seed, i), and the seed that
+ * tests i is selected before i, i.e. has higher priority.  So E is defined by
+ * d(higher priority, lower priority) < T — M3b and the overflow walk order each
+ * pair by `earlier` before the distance — and the lexicographically-first MIS
+ * on this E makes the greedy's decisions bit for bit: whether i joins seed s
+ * is the one test the greedy would have made.
+ *
+ * Cull bound.  d_H = 1 - sqrt(c) exp(-q / 4), q = dmu' (A + B)^-1 dmu, and
+ * c = sqrt(|A| |B|) / |(A + B) / 2| <= 1 (the determinant is log-concave).  So
+ * d_H < T gives exp(-q / 4) > 1 - T, q < -4 ln(1 - T), and the Mahalanobis
+ * form the culls bound, dmu' ((A + B) / 2)^-1 dmu = 2 q < -8 ln(1 - T) =: T_M.
+ * T_M replaces T wherever a cull quantity derives from minSeparation: the cell
+ * size R, the walk threshold thr (and with it merge_walk_cell's pre-test); the
+ * exact tests keep T.  No host-side quantity derives from minSeparation
+ * (DevCfg::walk_floor bounds the measurement pair walk, not the merge).
+ * In floats c <= 1 only holds up to rounding: the determinant of the product
+ * cancels, relative error <= ~10.5 u cond(A) cond(B).  Binned candidates have
+ * cond < 100 under this metric (cand_record), which puts the float distance
+ * within 2.2e-3 of the exact one (1.6e-3 from c, the rest from exp(-q / 4) with
+ * q <= 32); merge_cull_T therefore takes T + PHD_HELL_SLACK (4e-3) for T.  The
+ * existing 5 % margin stays for the roundings of the cull tests themselves.
+ * Worse-conditioned candidates are wild: tested exactly against everything.
+ * A pair whose sums or products leave the float range gives NaN or 1 — never
+ * an edge for T < 1 — so the bound is only needed where the floats behave.
+ *
+ * Serial triggers.  merge_cull_T is +inf for T >= 1 - slack, NaN for a NaN T,
+ * and above PHD_HELL_TM_MAX (T > 0.9956) the cell is 8 standard deviations wide
+ * and culls next to nothing: all three return -1 here, and the serial greedy,
+ * exact at any T, takes the particle.  The own-distance screen evaluates the
+ * Hellinger own-distance (own_distance_below<1>); NaN or >= T is `bad` as before.
  */
-template <int NT>
+template <int NT, int METRIC = 0>
 __device__ int merge_parallel(const MergeScratch& X, int K, float T, G1 float* dst, int cap, int Epool, int B, int* s_w,
                               float* s_wf, int* s_misc, int screen_bad, float screen_lmax, const UpdateArgs& a) {
     const int tid = threadIdx.x;
@@ -806,7 +850,13 @@ __device__ int merge_parallel(const MergeScratch& X, int K, float T, G1 float* d
     }
 #endif
     STAMP(11);
-    const float R = sqrtf(1.05f * T * lmax);
+    // the culls' threshold: T under metric 0, T_M under metric 1 (uniform)
+    float Tc = T;
+    if (METRIC != 0 && metric_hellinger<METRIC>()) {
+        Tc = merge_cull_T<METRIC>(T);
+        if (!(Tc <= PHD_HELL_TM_MAX)) return -1;  // T >= 1 - slack, NaN, or a degenerate lattice
+    }
+    const float R = sqrtf(1.05f * Tc * lmax);
     const float invR = (lmax > 0.f) ? 1.0f / (R * 1.001f) : 0.f;
     // M2: bucket counting sort of the binned candidates; wild ones go last.
     // Up to four candidates per thread (K <= 4 NT) each keeps its rank in its
@@ -905,7 +955,7 @@ __device__ int merge_parallel(const MergeScratch& X, int K, float T, G1 float* d
     STAMP(12);
     // M3a: candidate pairs (merge_walk), listed so the exact distance runs
     // densely in M3b instead of under a divergent mask.
-    const float thr = 1.05f * T * 0.5f;
+    const float thr = 1.05f * Tc * 0.5f;
     const int plcap = a.plreq > 0 ? min(X.plcap, a.plreq) : X.plcap;
     auto list_pair = [&](int i, int j) {
         const int sl = atomicAdd(s_misc + 2, 1);
@@ -913,7 +963,7 @@ __device__ int merge_parallel(const MergeScratch& X, int K, float T, G1 float* d
     };
     if (PHD_XK != 8) {
         if (cellw)
-            merge_walk_cell<NT>(X, K, Knw, Px, Py, lgPx, invR, thr, T, s_misc + 2, plcap);  // pairs of positions
+            merge_walk_cell<NT, METRIC>(X, K, Knw, Px, Py, lgPx, invR, thr, T, s_misc + 2, plcap);  // position pairs
         else
             merge_walk<NT>(X, K, Knw, B, Px, Py, lgPx, invR, thr, list_pair);
     }
@@ -965,7 +1015,16 @@ __device__ int merge_parallel(const MergeScratch& X, int K, float T, G1 float* d
 #pragma unroll
             for (int h = 0; h < H; h++) {
                 const int i = (int)(pr[h] >> 16), j = (int)(pr[h] & 0xffffu);
-                if (ok[h] && cand_mahal(X.K.P[i], vi[h], X.K.P[j], vj[h]) < T) {
+                bool edge;
+                if (METRIC != 0 && metric_hellinger<METRIC>()) {
+                    // the directed edge: the higher-priority candidate first, as the greedy passes its seed
+                    const float4 pi = X.K.P[i], pj = X.K.P[j];
+                    edge = ok[h] && (earlier(pi.z, i, pj.z, j) ? cand_dist<METRIC>(pi, vi[h], pj, vj[h])
+                                                               : cand_dist<METRIC>(pj, vj[h], pi, vi[h])) < T;
+                } else {
+                    edge = ok[h] && cand_mahal(X.K.P[i], vi[h], X.K.P[j], vj[h]) < T;
+                }
+                if (edge) {
                     const int sl = atomicAdd(s_misc, 1);
                     if (sl < Epool) X.edges[sl] = pr[h];
                     cnt16_inc(X.cur, i);
@@ -980,7 +1039,15 @@ __device__ int merge_parallel(const MergeScratch& X, int K, float T, G1 float* d
             s_misc[11] |= PHD_ST_PAIR_OVERFLOW;
         }
         merge_walk<NT>(Xo, K, Knw, B, Px, Py, lgPx, invR, thr, [&](int i, int j) {
-            if (cand_mahal(X.K.P[i], X.K.V(i), X.K.P[j], X.K.V(j)) < T) {
+            bool edge;
+            if (METRIC != 0 && metric_hellinger<METRIC>()) {  // (the directed edge, as M3b)
+                const float4 pi = X.K.P[i], pj = X.K.P[j];
+                edge = (earlier(pi.z, i, pj.z, j) ? cand_dist<METRIC>(pi, X.K.V(i), pj, X.K.V(j))
+                                                  : cand_dist<METRIC>(pj, X.K.V(j), pi, X.K.V(i))) < T;
+            } else {
+                edge = cand_mahal(X.K.P[i], X.K.V(i), X.K.P[j], X.K.V(j)) < T;
+            }
+            if (edge) {
                 const int sl = atomicAdd(s_misc, 1);
                 if (sl < Epool) X.edges[sl] = ((unsigned int)i << 16) | (unsigned int)j;
                 cnt16_inc(X.cur, i);
@@ -1372,7 +1439,7 @@ __device__ __forceinline__ void eta_term(unsigned long long* ehi, unsigned long 
 template <int NT>
 __device__ void rs_step_block(const RsStepArgs& a, unsigned char* smem);
 
-template <int NT, bool PRED, bool CPHD = false, int PART = 0>
+template <int NT, bool PRED, bool CPHD = false, int PART = 0, int METRIC = 0>
 __device__ __forceinline__ void update_body(const UpdateArgs& a) {
     static_assert(!CPHD || PART != 0, "the CPHD update runs as three launches (part A, k_cphd_terms, part C)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -2062,7 +2129,7 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a) {
             const int p = ncand + r;
             if (p < a.Kcap) {
                 const float4 vc = make_float4(v[3], v[4], v[5], v[6]);
-                X.K.P[p] = cand_record(v[1], v[2], w, vc, c.minSeparation, sc_bad, sc_lmax, (unsigned)k);
+                X.K.P[p] = cand_record<METRIC>(v[1], v[2], w, vc, c.minSeparation, sc_bad, sc_lmax, (unsigned)k);
             }
         }
         ncand += tot;
@@ -2108,7 +2175,8 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a) {
             const int p = ncand + r;
             if (p < a.Kcap) {
                 const float4 v = make_float4(e.cu0, e.cu1, e.cu2, e.cu3);
-                X.K.P[p] = cand_record(mx, my, w, v, c.minSeparation, sc_bad, sc_lmax, 0x8000u | (unsigned)(p - nd0));
+                X.K.P[p] = cand_record<METRIC>(mx, my, w, v, c.minSeparation, sc_bad, sc_lmax,
+                                               0x8000u | (unsigned)(p - nd0));
                 X.K.detv[p - nd0] = v;
             }
         }
@@ -2133,8 +2201,8 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a) {
                 float mean[2], cov[4];
                 d_birth(c, s_pose.px, s_pose.py, s_pose.ptheta, s_zr[m], s_zb[m], mean, cov);
                 const float4 v = make_float4(cov[0], cov[1], cov[2], cov[3]);
-                X.K.P[p] = cand_record(mean[0], mean[1], w, v, c.minSeparation, sc_bad, sc_lmax,
-                                       0x8000u | (unsigned)(p - nd0));
+                X.K.P[p] = cand_record<METRIC>(mean[0], mean[1], w, v, c.minSeparation, sc_bad, sc_lmax,
+                                               0x8000u | (unsigned)(p - nd0));
                 X.K.detv[p - nd0] = v;
             }
         }
@@ -2148,8 +2216,8 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a) {
             const int k = s_near[q];
             const G1 float* sk = prior(k);
             const float4 v = make_float4(sk[3 * a.cap], sk[4 * a.cap], sk[5 * a.cap], sk[6 * a.cap]);
-            X.K.P[p] = cand_record(sk[1 * a.cap], sk[2 * a.cap], sk[0], v, c.minSeparation, sc_bad, sc_lmax,
-                                   (unsigned)k);
+            X.K.P[p] = cand_record<METRIC>(sk[1 * a.cap], sk[2 * a.cap], sk[0], v, c.minSeparation, sc_bad, sc_lmax,
+                                           (unsigned)k);
         }
     }
     ncand += Gnear;
@@ -2163,11 +2231,12 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a) {
     /* Phase 5: greedy merge — parallel exact form, serial fallback. */
     int nout = (PHD_XK == 3 || PHD_XK == 4) ? 0
                : a.merge_mode != 0         ? -1
-                                           : merge_parallel<NT>(X, ncand, c.minSeparation, dst, a.cap, a.Epool,
-                                                                a.Bbuckets, s_scr, s_redf, s_cnt + 3, sc_bad, sc_lmax, a);
+                                           : merge_parallel<NT, METRIC>(X, ncand, c.minSeparation, dst, a.cap, a.Epool,
+                                                                        a.Bbuckets, s_scr, s_redf, s_cnt + 3, sc_bad,
+                                                                        sc_lmax, a);
     if (nout < 0) {
         __syncthreads();
-        nout = merge_serial<NT>(X.K, nullptr, ncand, X.par, c.minSeparation, dst, a.cap, s_red, s_redf);
+        nout = merge_serial<NT, METRIC>(X.K, nullptr, ncand, X.par, c.minSeparation, dst, a.cap, s_red, s_redf);
         flags |= PHD_ST_SERIAL_MERGE;
     }
 
@@ -2271,6 +2340,22 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))
 }
 __global__ void __launch_bounds__(512) PHD_CPHD_WPE k_update_cphd_c_512(UpdateArgs a) { update_body<512, false, true, 2>(kargs(a)); }
 __global__ void __launch_bounds__(1024) k_update_cphd_c_1024(UpdateArgs a) { update_body<1024, false, true, 2>(kargs(a)); }
+/* distance_metric 1 (Hellinger): the launches that hold the merge, with the
+ * metric a template parameter — the metric-0 kernels above keep their code and
+ * registers.  No wave-per-SIMD targets here: the distance's double-precision
+ * exp needs more registers than part C's 80, and a spill into scratch costs
+ * more than the occupancy it would buy. */
+__global__ void __launch_bounds__(256) k_update_fused_256_h(UpdateArgs a) { update_body<256, false, false, 0, 1>(kargs(a)); }
+__global__ void __launch_bounds__(512) k_update_fused_512_h(UpdateArgs a) { update_body<512, false, false, 0, 1>(kargs(a)); }
+__global__ void __launch_bounds__(1024) k_update_fused_1024_h(UpdateArgs a) { update_body<1024, false, false, 0, 1>(kargs(a)); }
+__global__ void __launch_bounds__(256) k_update_fused_p256_h(UpdateArgs a) { update_body<256, true, false, 0, 1>(kargs(a)); }
+__global__ void __launch_bounds__(512) k_update_fused_p512_h(UpdateArgs a) { update_body<512, true, false, 0, 1>(kargs(a)); }
+__global__ void __launch_bounds__(256) k_update_phd_c_256_h(UpdateArgs a) { update_body<256, false, false, 2, 1>(kargs(a)); }
+__global__ void __launch_bounds__(512) k_update_phd_c_512_h(UpdateArgs a) { update_body<512, false, false, 2, 1>(kargs(a)); }
+__global__ void __launch_bounds__(1024) k_update_phd_c_1024_h(UpdateArgs a) { update_body<1024, false, false, 2, 1>(kargs(a)); }
+__global__ void __launch_bounds__(256) k_update_cphd_c_256_h(UpdateArgs a) { update_body<256, false, true, 2, 1>(kargs(a)); }
+__global__ void __launch_bounds__(512) k_update_cphd_c_512_h(UpdateArgs a) { update_body<512, false, true, 2, 1>(kargs(a)); }
+__global__ void __launch_bounds__(1024) k_update_cphd_c_1024_h(UpdateArgs a) { update_body<1024, false, true, 2, 1>(kargs(a)); }
 
 /* -------------------------------------------------------- normalise, nEff */
 
