@@ -126,7 +126,9 @@ __device__ __forceinline__ void cphd_wave(const UpdateArgs& a, int n, int M, con
     WSTAMP(30);
     /* <Psi1d_m, p> = log sum_a P_m[a] T_m[a] (prefix products P, suffix sums T;
      * positive recursions), by segments of L measurements: the T chain runs
-     * down from M-1 and the P chain up from 0 side by side (independent). */
+     * down from M-1 and the P chain up from 0 side by side (independent).
+     * M <= 64: the unrolled steps of a segment carry no m < M test — λ'_m = 0
+     * there (lp, lanes >= M; m <= 63), and fma(0, x, P) = P bit for bit. */
     if (M <= 64) {
         constexpr int L = 16;
         const double lp = lane < M ? lampa[lane] : 0.0;
@@ -138,22 +140,22 @@ __device__ __forceinline__ void cphd_wave(const UpdateArgs& a, int n, int M, con
             for (int s = 0; s < max(nT, nP); s++) {
                 if (s < nT) {
                     const int m = M - 1 - s;
-                    T = fma(readlane_d(lp, m), dpp_or_zero_d<0x130, 0xf>(T), T);
+                    T = fma(readlane_d(lp, m), dpp_full_d<0x130>(T), T);
                 }
-                if (s < nP) P = fma(readlane_d(lp, s), dpp_or_zero_d<0x138, 0xf>(P), P);
+                if (s < nP) P = fma(readlane_d(lp, s), dpp_full_d<0x138>(P), P);
             }
             double tr[L];
 #pragma unroll
             for (int q = L - 1; q >= 0; q--) {
                 const int m = m0 + q;
                 tr[q] = T;
-                if (m < m1 && m > m0) T = fma(readlane_d(lp, m), dpp_or_zero_d<0x130, 0xf>(T), T);
+                if (q > 0) T = fma(readlane_d(lp, m), dpp_full_d<0x130>(T), T);
             }
 #pragma unroll
             for (int q = 0; q < L; q++) {
                 const int m = m0 + q;
                 tr[q] *= P;
-                if (m < m1) P = fma(readlane_d(lp, m), dpp_or_zero_d<0x138, 0xf>(P), P);
+                P = fma(readlane_d(lp, m), dpp_full_d<0x138>(P), P);
             }
 #pragma unroll
             for (int q = 0; q < L; q++) tr[q] = wave_sum_dx(tr[q]);
@@ -327,6 +329,7 @@ __device__ bool cphd_fast64(const UpdateArgs& a, int n, int M, const u64* ehi, c
     const int lane = threadIdx.x & 63;
     const int Nmax = a.Nmax;
     if (M > 64 || M < 1) return false;
+    WSTAMP(35);
     win = uni_d(win);
     qd = uni_d(qd);
     W = uni_d(W);
@@ -349,11 +352,19 @@ __device__ bool cphd_fast64(const UpdateArgs& a, int n, int M, const u64* ehi, c
     const double lmax = wave_max_dx(lam0);
     const double lsum = wave_sum_dx(lane < M ? lam0 : 0.0);
     const double lp = lam0 == -INFINITY ? 0.0 : exp(lam0 - lmax);  // λ'_m, lane m
-    // λ' of every measurement in LDS: the chains below read λ'_m as a broadcast
-    // LDS load (issued ahead of the chain) instead of two v_readlane each
-    __shared__ double s_lp[64];
-    s_lp[lane] = lp;
-    wsync();  // (one wave: no workgroup barrier, so a larger workgroup's wave 0 can run it alone)
+    /* The chains below run all 64 lanes' worth of steps whatever M is: λ'_m = 0
+     * for m >= M (lam0 = -inf there), and fma(0, x, P) = P bit for bit for the
+     * finite P and x of these recursions (coefficients bounded by binomials of
+     * λ' <= 1) — straight-line code, no per-step test.  λ'_m is read a batch of
+     * 8 steps ahead of its use as two v_readlane into a scalar pair, the FMA's
+     * scalar operand: no step waits for memory, and the readlanes issue in the
+     * wait states between an FMA and the DPP moves that read its result.  Each
+     * batch reads through its own opaque copy of lp: the four passes read every
+     * lane, and readlanes shared between them would be kept live from the
+     * first pass to the last, past the scalar registers (spilled to VGPR lanes). */
+    double lpb = lp;
+#define PHD_LP(m) readlane_d(lpb, m)
+#define PHD_LP_BATCH() asm volatile("" : "+v"(lpb))
     auto lB0f = [&](int j) { return Nmax - j >= 0 ? (j == 0 ? 0.0 : (double)j * dd) - W + lSc : -INFINITY; };
     auto lB1f = [&](int j) { return Nmax - j - 1 >= 0 ? (double)(j + 1) * dd - W + lSc : -INFINITY; };
     double bv = -INFINITY;
@@ -365,6 +376,7 @@ __device__ bool cphd_fast64(const UpdateArgs& a, int n, int M, const u64* ehi, c
     double T = (bv == -INFINITY || bmax == -INFINITY) ? 0.0 : exp(bv - bmax);  // T_{M-1} = β'
     double ipm = 0.0;   // lane m: Σ_a P_m[a] T_m[a] (scaled by e^-bmax)
     double Pfull = 0.0; // P_M: the ESF of all Λ' (lane k: coefficient k)
+    WSTAMP(36);
 #pragma unroll
     for (int h = 1; h >= 0; h--) {  // measurements [32h, 32h + 32): P_m stored for this half
         double Pst_r[PST_LDS ? 1 : 32];
@@ -374,26 +386,39 @@ __device__ bool cphd_fast64(const UpdateArgs& a, int n, int M, const u64* ehi, c
         };
         double P = lane == 0 ? 1.0 : 0.0;
 #pragma unroll
-        for (int m = 0; m < 32 * h + 32; m++) {
-            if (m >= 32 * h) Pst(m - 32 * h) = P;
-            if (m < M) P = fma(s_lp[m], dpp_or_zero_d<0x138, 0xf>(P), P);
+        for (int m0 = 0; m0 < 32 * h + 32; m0 += 8) {
+            double l[8];
+            PHD_LP_BATCH();
+#pragma unroll
+            for (int q = 0; q < 8; q++) l[q] = PHD_LP(m0 + q);
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const int m = m0 + q;
+                if (m >= 32 * h) Pst(m - 32 * h) = P;
+                P = fma(l[q], dpp_full_d<0x138>(P), P);  // wave_shr:1, lane 0 <- 0
+            }
         }
         if (h == 1) Pfull = P;
 #pragma unroll
         for (int b = 3; b >= 0; b--) {  // batches of 8 measurements, descending
-            double x[8];
+            const int m0 = 32 * h + 8 * b;
+            double l[8], x[8];
+            PHD_LP_BATCH();
+#pragma unroll
+            for (int q = 0; q < 8; q++) l[q] = PHD_LP(m0 + q);
 #pragma unroll
             for (int q = 7; q >= 0; q--) {
-                const int m = 32 * h + 8 * b + q;
-                x[q] = m < M ? Pst(m - 32 * h) * T : 0.0;
-                if (m < M) T = fma(s_lp[m], dpp_or_zero_d<0x130, 0xf>(T), T);
+                x[q] = Pst(m0 + q - 32 * h) * T;  // (m >= M: finite, summed into lanes >= M of ipm, never read)
+                T = fma(l[q], dpp_full_d<0x130>(T), T);  // wave_shl:1, lane 63 <- 0
             }
             const double sum = wave_sum8_d(x);  // lane L: measurement 32h + 8b + (L >> 3)
-            const int m0 = 32 * h + 8 * b;
             const double mine = __shfl(sum, ((lane - m0) & 7) << 3, 64);
             if (lane >= m0 && lane < m0 + 8) ipm = mine;
         }
+        WSTAMP(38 - h);
     }
+#undef PHD_LP
+#undef PHD_LP_BATCH
     // b_k = log of the hypothesis terms (k <= M; k = 64 is a scalar when M = 64)
     double bk = -INFINITY, p0 = -INFINITY, q0 = -INFINITY;
     if (lane <= M) {
@@ -436,6 +461,7 @@ __device__ bool cphd_fast64(const UpdateArgs& a, int n, int M, const u64* ehi, c
     out.ip1 = ip1;
     out.bmax = bmax;
     out.wide = __ballot(wide != 0) != 0ull;
+    WSTAMP(39);
     return true;
 }
 

@@ -129,6 +129,16 @@ __device__ __forceinline__ double dpp_or_zero_d(double v) {
     return __hiloint2double(dpp_or_zero<CTRL, ROWMASK>(hi), dpp_or_zero<CTRL, ROWMASK>(lo));
 }
 
+/* dpp_or_zero_d with every row and bank enabled (a whole-wave shift): the lane
+ * without a source reads 0 from the DPP bound control, so the destination
+ * needs no zero fill first.  Full masks only — under a partial row mask the
+ * masked rows keep the old value, which the scans need (dpp_or_zero_d). */
+template <int CTRL>
+__device__ __forceinline__ double dpp_full_d(double v) {
+    return __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true),
+                            __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true));
+}
+
 /* inclusive scan in double; lane 63 holds the wave total */
 __device__ __forceinline__ double wave_incl_scan_d(double x) {
     x += dpp_or_zero_d<0x111, 0xf>(x);
