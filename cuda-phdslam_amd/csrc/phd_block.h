@@ -98,18 +98,19 @@ __device__ __forceinline__ int first_argmax_block(float bw, int bi) {
 
 /* The expected pose Σ exp(w_i) pose_i (main.cpp:331-347; thread t accumulates
  * entries t, t + blockDim, ... in double, block_reduce_1024 per field) and the
- * first arg-max of w, where w_of(i) is entry i's normalised log-weight.
- * ep and the returned index are valid on thread 0.  s: 32 doubles. */
-template <class W>
-__device__ __forceinline__ int expected_pose_block(int n, W&& w_of, const phd_pose* __restrict__ pose, float (&ep)[6],
-                                                   double* s) {
+ * first arg-max of w, where w_of(i) is entry i's normalised log-weight and
+ * pose_of(i) points to its 6 pose floats (the sharded trace reads them from the
+ * ranks' gathered blocks).  ep and the returned index are valid on thread 0.
+ * s: 32 doubles. */
+template <class W, class P>
+__device__ __forceinline__ int expected_pose_block_at(int n, W&& w_of, P&& pose_of, float (&ep)[6], double* s) {
     double acc[6] = {0, 0, 0, 0, 0, 0};
     float bw = -FLT_MAX;
     int bi = INT_MAX;
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         const float w = w_of(i);
         const float ew = expf(w);
-        const float* ps = (const float*)&pose[i];
+        const float* ps = pose_of(i);
         for (int k = 0; k < 6; k++) acc[k] += (double)(ew * ps[k]);
         if (w > bw) {
             bw = w;
@@ -118,6 +119,11 @@ __device__ __forceinline__ int expected_pose_block(int n, W&& w_of, const phd_po
     }
     for (int k = 0; k < 6; k++) ep[k] = (float)block_reduce_1024<double>(acc[k], s, false);
     return first_argmax_block(bw, bi);
+}
+template <class W>
+__device__ __forceinline__ int expected_pose_block(int n, W&& w_of, const phd_pose* __restrict__ pose, float (&ep)[6],
+                                                   double* s) {
+    return expected_pose_block_at(n, w_of, [&](int i) { return (const float*)&pose[i]; }, ep, s);
 }
 
 /* nEff (main.cpp:1281-1284) from s2 = Σ exp(2 w) of the n normalised entries

@@ -206,7 +206,10 @@ struct phd_ctx {
         float* d_w = nullptr;
         double* d_part = nullptr;
         int* d_hand = nullptr;
+        float* d_card_row = nullptr;  // sharded trace: the arg-max particle's row before it is packed
+        bool shard_packed = false;    // phd_trace_shard_pack enqueued, its phd_trace_shard_append not yet
     } tr;
+    hipEvent_t ev_trace = nullptr;  // sharded trace: the gathered log-weights (plan stream) before the pack
 };
 
 static int set_device(phd_ctx* c) {
@@ -408,7 +411,8 @@ static ZBlk zblk_layout() {
 }
 
 static void trace_free(phd_ctx* c) {
-    void* ptrs[] = {c->tr.d_rec, c->tr.d_snap, c->tr.d_card, c->tr.d_card_all, c->tr.d_w, c->tr.d_part, c->tr.d_hand};
+    void* ptrs[] = {c->tr.d_rec, c->tr.d_snap, c->tr.d_card, c->tr.d_card_all, c->tr.d_w, c->tr.d_part, c->tr.d_hand,
+                    c->tr.d_card_row};
     for (void* p : ptrs)
         if (p) hipFree(p);
     c->tr = {};
@@ -438,6 +442,7 @@ static int ctx_free(phd_ctx* c) {
     if (c->ev_terms) hipEventDestroy(c->ev_terms);
     if (c->ev_logw) hipEventDestroy(c->ev_logw);
     if (c->ev_plan) hipEventDestroy(c->ev_plan);
+    if (c->ev_trace) hipEventDestroy(c->ev_trace);
     if (c->ev_rs) hipEventDestroy(c->ev_rs);
     if (c->aux) hipStreamDestroy(c->aux);
     for (auto e : c->ev_a) hipEventDestroy(e);
@@ -1948,13 +1953,22 @@ int phd_predict_update(phd_ctx* ctx, const phd_ackerman_control* u, int do_predi
 }
 
 /* what the trace does not cover (phd_trace_enable, and again at every traced
- * step: the configuration may change in between) */
-static int trace_supported(const phd_ctx* ctx) {
+ * step: the configuration may change in between).  sharded: the trace of a
+ * sharded step (phd_trace_shard_pack), which reads migrated slabs but not every
+ * rank's cardinality rows; phd_step's own reads no migrated slab.
+ * phd_trace_enable asks for neither: the context may serve either step. */
+enum TraceUse { TRACE_ENABLE, TRACE_STEP, TRACE_SHARDED };
+static int trace_supported(const phd_ctx* ctx, TraceUse use) {
     if (ctx->cfg.featureModel != PHD_FEATURE_STATIC)
         return fail(PHD_E_UNSUPPORTED, "the estimate trace supports the static feature model only");
     if (ctx->cfg.nPredictParticles > 1 || ctx->n != ctx->n_base)
         return fail(PHD_E_UNSUPPORTED, "the estimate trace does not support n_predict_particles > 1");
-    if (ctx->d_map_x) return fail(PHD_E_UNSUPPORTED, "the estimate trace does not support migrated (sharded) slabs");
+    if (use == TRACE_STEP && ctx->d_map_x)
+        return fail(PHD_E_UNSUPPORTED, "phd_step's estimate trace does not support migrated (sharded) slabs");
+    if (use == TRACE_SHARDED && ctx->tr.d_card && (ctx->cfg.mapEstimate & 2))
+        return fail(PHD_E_UNSUPPORTED,
+                    "the sharded estimate trace does not support PHD_TRACE_CARD_DIST with map_estimate & 2 (the "
+                    "expected rows are a sequential sum over every rank's particles)");
     if ((ctx->tr.flags & PHD_TRACE_CARD_DIST) &&
         (ctx->cfg.filterType != PHD_FILTER_CPHD || ctx->cfg.maxCardinality + 1 != ctx->tr.K))
         return fail(PHD_E_UNSUPPORTED, "PHD_TRACE_CARD_DIST needs the CPHD configuration it was enabled with");
@@ -2022,7 +2036,7 @@ int phd_trace_enable(phd_ctx* ctx, int capacity, int map_snapshot_cap, unsigned 
     auto& T = ctx->tr;
     T.flags = flags;
     T.K = (flags & PHD_TRACE_CARD_DIST) ? ctx->cfg.maxCardinality + 1 : 0;
-    int rc = trace_supported(ctx);
+    int rc = trace_supported(ctx, TRACE_ENABLE);
     if ((flags & PHD_TRACE_CARD_DIST) && !rc && T.K < 1) rc = fail(PHD_E_ARG, "CPHD needs max_cardinality >= 0");
     if (rc) {
         T = {};
@@ -2036,6 +2050,7 @@ int phd_trace_enable(phd_ctx* ctx, int capacity, int map_snapshot_cap, unsigned 
     if (e == hipSuccess && map_snapshot_cap > 0)
         e = hipMalloc((void**)&T.d_snap, (size_t)capacity * map_snapshot_cap * sizeof(phd_gaussian2d));
     if (e == hipSuccess && T.K) e = hipMalloc((void**)&T.d_card, (size_t)capacity * T.K * sizeof(float));
+    if (e == hipSuccess && T.K) e = hipMalloc((void**)&T.d_card_row, T.K * sizeof(float));
     if (e == hipSuccess && T.K && (ctx->cfg.mapEstimate & 2))
         e = hipMalloc((void**)&T.d_card_all, N * T.K * sizeof(float));
     if (e == hipSuccess) e = hipMemsetAsync(T.d_rec, 0, (size_t)capacity * sizeof(phd_trace_record), ctx->stream);
@@ -2090,6 +2105,104 @@ int phd_trace_read(phd_ctx* ctx, long first, int count, phd_trace_record* record
     return PHD_OK;
 }
 
+int phd_trace_shape(phd_ctx* ctx, int* capacity, int* map_snapshot_cap, int* card_k) {
+    if (!ctx) return fail(PHD_E_ARG, "null ctx");
+    if (capacity) *capacity = ctx->tr.cap;
+    if (map_snapshot_cap) *map_snapshot_cap = ctx->tr.snap_cap;
+    if (card_k) *card_k = ctx->tr.d_card ? ctx->tr.K : 0;
+    return PHD_OK;
+}
+
+int phd_trace_shard_block_bytes(int n, int map_snapshot_cap, int K, size_t* bytes) {
+    if (n < 1 || map_snapshot_cap < 0 || K < 0 || !bytes) return fail(PHD_E_ARG, "bad arguments to phd_trace_shard_block_bytes");
+    *bytes = trace_block_words(n, map_snapshot_cap, K) * sizeof(float);
+    return PHD_OK;
+}
+
+/* the arguments the three stages of a sharded trace share */
+static TraceShardArgs trace_shard_args(phd_ctx* ctx, const float* dev_w_all, int world, int rank) {
+    auto& T = ctx->tr;
+    const size_t slot = (size_t)(T.count % T.cap);
+    TraceShardArgs a{};
+    a.w_all = dev_w_all;
+    a.world = world;
+    a.rank = rank;
+    a.pose = ctx->d_pose;
+    a.src = ctx->d_src;
+    a.map_in = ctx->d_map[ctx->cur];
+    a.size_in = ctx->d_size[ctx->cur];
+    a.map_x = ctx->d_map_x;
+    a.size_x = ctx->d_size_x;
+    a.n = ctx->n;
+    a.cap = ctx->cap.map_capacity;
+    a.M = ctx->M;
+    a.has_meas = rs_mode(ctx);
+    a.resample_thresh = ctx->cfg.resampleThresh;
+    a.err = ctx->d_err;
+    a.hand = T.d_hand;
+    a.snap_cap = T.snap_cap;
+    a.K = T.d_card ? T.K : 0;
+    a.block_words = trace_block_words(ctx->n, a.snap_cap, a.K);
+    a.rec = T.d_rec + slot;
+    a.snap = T.d_snap ? T.d_snap + slot * (size_t)T.snap_cap : nullptr;
+    a.card = T.d_card ? T.d_card + slot * (size_t)T.K : nullptr;
+    return a;
+}
+
+static int trace_shard_check(phd_ctx* ctx, const void* dev_w_all, const void* dev_block, int world, int rank,
+                             const char* who) {
+    if (!ctx || !dev_w_all || !dev_block || world < 1 || world > 1024 || rank < 0 || rank >= world ||
+        (long long)world * ctx->n > (long long)RS_MAX_CHUNKS * RS_THREADS)
+        return fail(PHD_E_ARG, std::string("bad arguments to ") + who);
+    if (!ctx->cfg_set || ctx->tr.cap <= 0) return fail(PHD_E_ARG, "the estimate trace is off (phd_trace_enable)");
+    return PHD_OK;
+}
+
+int phd_trace_shard_pack(phd_ctx* ctx, const float* dev_w_all, int world, int rank, uint64_t step, void* dev_block) {
+    int rc = trace_shard_check(ctx, dev_w_all, dev_block, world, rank, "phd_trace_shard_pack");
+    if (rc) return rc;
+    rc = trace_supported(ctx, TRACE_SHARDED);
+    if (rc) return rc;
+    if (ctx->tr.shard_packed) return fail(PHD_E_ARG, "phd_trace_shard_append the previous block first");
+    if (set_device(ctx)) return PHD_E_HIP;
+    auto& T = ctx->tr;
+    if (ctx->plan_stream) {
+        // the caller gathered dev_w_all on the plan stream (beside part C): the
+        // trace runs on the context stream, after the update and after that gather
+        if (!ctx->ev_trace) HIPCHK(hipEventCreateWithFlags(&ctx->ev_trace, kEvOrder));
+        HIPCHK(hipEventRecord(ctx->ev_trace, ctx->plan_stream));
+        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_trace, 0));
+    }
+    TraceShardArgs a = trace_shard_args(ctx, dev_w_all, world, rank);
+    a.step = step;
+    a.block = (float*)dev_block;
+    trace_launch_shard_weights(a, ctx->stream);
+    if (T.d_card && ctx->cn_valid) {  // the arg-max particle's row, where this rank owns it (stage 1 left its slab)
+        hipLaunchKernelGGL(k_cphd_cardinality, dim3(1), dim3(256), 0, ctx->stream,
+                           (const int*)(T.d_hand + TRACE_H_SLAB), (const double*)ctx->d_cn_coef,
+                           (const double*)ctx->d_cn_x, ctx->cn_stride, ctx->d_lfact, T.K - 1, 1, T.d_card_row);
+        a.card_row = T.d_card_row;
+    }
+    trace_launch_shard_pack(a, ctx->stream);
+    HIPCHK(hipGetLastError());
+    T.shard_packed = true;
+    return PHD_OK;
+}
+
+int phd_trace_shard_append(phd_ctx* ctx, const float* dev_w_all, const void* dev_blocks_all, int world, int rank) {
+    int rc = trace_shard_check(ctx, dev_w_all, dev_blocks_all, world, rank, "phd_trace_shard_append");
+    if (rc) return rc;
+    if (!ctx->tr.shard_packed) return fail(PHD_E_ARG, "phd_trace_shard_append without phd_trace_shard_pack");
+    if (set_device(ctx)) return PHD_E_HIP;
+    TraceShardArgs a = trace_shard_args(ctx, dev_w_all, world, rank);
+    a.blocks = (const float*)dev_blocks_all;
+    trace_launch_shard_finish(a, ctx->stream);
+    HIPCHK(hipGetLastError());
+    ctx->tr.shard_packed = false;
+    ctx->tr.count++;
+    return PHD_OK;
+}
+
 int phd_step(phd_ctx* ctx, const phd_ackerman_control* u, int do_predict, uint64_t step, float* neff_out,
              int* resampled) {
     if (!ctx) return fail(PHD_E_ARG, "null ctx");
@@ -2112,7 +2225,7 @@ int phd_step(phd_ctx* ctx, const phd_ackerman_control* u, int do_predict, uint64
     // resample rewrites: its resample runs after the update and the trace
     const bool traced = ctx->tr.cap > 0;
     if (traced) {
-        int rc0 = trace_supported(ctx);
+        int rc0 = trace_supported(ctx, TRACE_STEP);
         if (rc0) return rc0;
     }
     const bool overlap = !traced &&
@@ -2452,7 +2565,9 @@ int phd_shard_resample_async(phd_ctx* ctx, float* dev_w_all, int world, int rank
         // once beside part C's, and its latency is hidden.  The pack, which reads
         // the posterior maps, waits for it on the context stream.
         if (!ctx->ev_plan) HIPCHK(hipEventCreateWithFlags(&ctx->ev_plan, kEvOrder));
-        if (!ctx->src_fresh) {  // (no update since the last remap: after the whole stream)
+        // (no update since the last remap: after the whole stream; a traced step:
+        // after its trace, which reads dev_w_all before the plan normalises it in place)
+        if (!ctx->src_fresh || ctx->tr.cap > 0) {
             HIPCHK(hipEventRecord(ctx->ev_plan, ctx->stream));
             HIPCHK(hipStreamWaitEvent(ctx->plan_stream, ctx->ev_plan, 0));
         }

@@ -50,6 +50,8 @@ struct Rank {
     unsigned char* recv_blocks = nullptr;
     unsigned char* ovf_send = nullptr;     // ovf_capacity * record_bytes
     unsigned char* ovf_recv = nullptr;     // n * record_bytes
+    unsigned char* tr_block = nullptr;     // trace_bytes (phd_group_trace_enable)
+    unsigned char* tr_blocks = nullptr;    // world * trace_bytes
     std::vector<long long> sends, recvs;   // overflow (peer, offset, bytes) triples of the open plan
 };
 
@@ -59,6 +61,7 @@ struct phd_group {
     int world = 0, n = 0, K = 0;  // world: ranks of the whole group (r.size(): the ranks this process drives)
     size_t rec = 0;
     int ovf_capacity = 0;
+    size_t trace_bytes = 0;  // a rank's trace block (0: the trace is off)
     uint64_t seed = 0;
     float new_logw = 0.f;
     bool open = false;
@@ -122,7 +125,7 @@ int phd_group_overflow_slices(int world, const int* send_records, const int* rec
 static void free_rank(Rank& k) {
     (void)hipSetDevice(k.device);
     void* p[] = {k.w_local, k.w_all, k.parents, k.keep_src, k.send_src, k.recv_rec,
-                 k.send_blocks, k.recv_blocks, k.ovf_send, k.ovf_recv};
+                 k.send_blocks, k.recv_blocks, k.ovf_send, k.ovf_recv, k.tr_block, k.tr_blocks};
     for (void* q : p)
         if (q) (void)hipFree(q);
     if (k.comm) ncclCommDestroy(k.comm);
@@ -358,6 +361,15 @@ int phd_group_step(phd_group* g, const phd_ackerman_control* u, uint64_t step, f
     for (Rank& k : g->r)
         NCCLCHK(ncclAllGather(k.w_local, k.w_all, (size_t)g->n, ncclFloat32, k.comm, k.aux ? k.aux : k.st));
     NCCLCHK(ncclGroupEnd());
+    // (trace on) every rank's trace block, their all-gather, the scan's record:
+    // from the store the plan is about to remap and the log-weights it normalises
+    if (g->trace_bytes) {
+        for (Rank& k : g->r) PHDCHK(phd_trace_shard_pack(k.ctx, k.w_all, W, k.rank, step, k.tr_block));
+        NCCLCHK(ncclGroupStart());
+        for (Rank& k : g->r) NCCLCHK(ncclAllGather(k.tr_block, k.tr_blocks, g->trace_bytes, ncclUint8, k.comm, k.st));
+        NCCLCHK(ncclGroupEnd());
+        for (Rank& k : g->r) PHDCHK(phd_trace_shard_append(k.ctx, k.w_all, k.tr_blocks, W, k.rank));
+    }
     // 4. the global plan, identical on every rank; the fixed blocks packed
     for (Rank& k : g->r)
         PHDCHK(phd_shard_resample_async(k.ctx, k.w_all, W, k.rank, g->seed, step, k.parents, k.keep_src, k.send_src,
@@ -381,6 +393,31 @@ int phd_group_step(phd_group* g, const phd_ackerman_control* u, uint64_t step, f
     // 6. received records into the deficit slots
     if (W > 1)
         for (Rank& k : g->r) PHDCHK(phd_shard_receive_blocks(k.ctx, k.recv_blocks, g->K, k.recv_rec));
+    return PHD_OK;
+}
+
+int phd_group_trace_enable(phd_group* g, int capacity, int map_snapshot_cap, unsigned flags) {
+    if (!g) return gfail(PHD_E_ARG, "null group");
+    for (Rank& k : g->r) {
+        (void)hipSetDevice(k.device);
+        (void)hipStreamSynchronize(k.st);
+        if (k.tr_block) (void)hipFree(k.tr_block);
+        if (k.tr_blocks) (void)hipFree(k.tr_blocks);
+        k.tr_block = k.tr_blocks = nullptr;
+    }
+    g->trace_bytes = 0;
+    size_t bytes = 0;
+    for (Rank& k : g->r) {
+        PHDCHK(phd_trace_enable(k.ctx, capacity, map_snapshot_cap, flags));
+        if (!capacity) continue;
+        int card_k = 0;
+        PHDCHK(phd_trace_shape(k.ctx, nullptr, nullptr, &card_k));
+        PHDCHK(phd_trace_shard_block_bytes(g->n, map_snapshot_cap, card_k, &bytes));
+        HIPCHKG(hipSetDevice(k.device));
+        HIPCHKG(hipMalloc((void**)&k.tr_block, bytes));
+        HIPCHKG(hipMalloc((void**)&k.tr_blocks, bytes * g->world));
+    }
+    g->trace_bytes = bytes;
     return PHD_OK;
 }
 

@@ -1,6 +1,7 @@
 /*
  * phd_trace.h — launch interface of the per-scan estimate trace (phd_trace.hip),
- * called by phd_step (phd_capi.hip) between the update and the resample.
+ * called by phd_step (phd_capi.hip) between the update and the resample, and
+ * of its sharded form, called by phd_trace_shard_pack / phd_trace_shard_append.
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,6 +19,7 @@ namespace phd {
 #define TRACE_H_PARTICLE 0 /* arg-max particle */
 #define TRACE_H_SLAB 1     /* its slab reference (src[particle]) */
 #define TRACE_H_ERRPREV 2  /* the status-error counter after the previous traced step */
+#define TRACE_H_LSE 3      /* sharded trace: the log-sum-exp of the gathered log-weights (float bits) */
 #define TRACE_H_WORDS 4
 
 struct TraceArgs {
@@ -55,5 +57,62 @@ void trace_launch_stage1(const TraceArgs& a, hipStream_t st);
 /* Stage 2 (posterior maps written): cardinalities by blocks of particles, then
  * the fixed-order combine, the snapshot and the expected cardinality rows. */
 void trace_launch_stage2(const TraceArgs& a, hipStream_t st);
+
+/* ---- the trace of a sharded step (phd_trace_shard_pack / _append, phd_capi.h) ----
+ * Every rank writes one fixed-size block, a flat run of 32-bit words:
+ *   [0, 16)                 header, TRACE_BH_*; the other words zero
+ *   [16, 16 + 6n)           the n local poses
+ *   [.., + n)               the n local cardinalities, (float) Σ_j w_j
+ *   [.., + 7 snap_cap)      the arg-max particle's map snapshot, phd_gaussian2d words
+ *   [.., + K)               its cardinality row
+ * rounded up to 4 words.  Snapshot and row are zero on the ranks that do not
+ * own the arg-max particle.  The all-gathered blocks sit in rank order. */
+#define TRACE_BH_WORDS 16
+#define TRACE_BH_ERR 0   /* growth of the rank's status-error counter since its previous traced step */
+#define TRACE_BH_OWNER 1 /* 1 on the rank that owns the arg-max particle */
+#define TRACE_BH_SIZE 2  /* owner: components of that particle's map */
+#define TRACE_BH_CARD 3  /* owner: its cardinality (float) */
+
+inline size_t trace_block_words(int n, int snap_cap, int K) {
+    const size_t w = TRACE_BH_WORDS + (size_t)(6 + 1) * n + (size_t)7 * snap_cap + (size_t)K;
+    return (w + 3) & ~(size_t)3;
+}
+
+struct TraceShardArgs {
+    const float* w_all; /* the world * n gathered un-normalised log-weights, rank order */
+    int world, rank;
+    /* this rank's store, as k_cardinality reads it */
+    const phd_pose* pose;
+    const int* src;
+    const float* map_in;
+    const int* size_in;
+    const float* map_x;
+    const int* size_x;
+    int n, cap;
+    /* the scan */
+    uint64_t step;
+    int M, has_meas;
+    float resample_thresh;
+    const int* err;
+    int* hand;             /* TRACE_H_* */
+    const float* card_row; /* the cardinality row of slab hand[TRACE_H_SLAB] (NULL: none) */
+    int snap_cap, K;
+    size_t block_words;
+    float* block;        /* pack: this rank's block */
+    const float* blocks; /* finish: the world gathered blocks */
+    /* this scan's ring entries */
+    phd_trace_record* rec;
+    phd_gaussian2d* snap;
+    float* card;
+};
+
+/* Stage 1 (w_all gathered): one 1024-thread workgroup, k_trace_weights'
+ * arithmetic over all world * n entries; starts the record. */
+void trace_launch_shard_weights(const TraceShardArgs& a, hipStream_t st);
+/* Stage 2 (posterior maps written, before the plan's remap): this rank's block. */
+void trace_launch_shard_pack(const TraceShardArgs& a, hipStream_t st);
+/* Stage 4 (blocks gathered): the cross-rank sums in the single context's order
+ * and the owner's entries; completes the record. */
+void trace_launch_shard_finish(const TraceShardArgs& a, hipStream_t st);
 
 }  // namespace phd

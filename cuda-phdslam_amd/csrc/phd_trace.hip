@@ -15,6 +15,10 @@
  *            each map by one wave (k_cardinality's sum), weighted partials
  *            k_trace_finish    the fixed-order combine, the map snapshot and
  *            the expected cardinality rows
+ * The sharded step's trace (phd_trace_shard_pack / _append, below): the same
+ * record from all world * n particles — k_trace_shard_weights on the gathered
+ * log-weights, k_trace_shard_pack into this rank's block, the caller's
+ * all-gather of the blocks, k_trace_shard_finish.
  * No float atomics anywhere: a run reproduces its records bit for bit.
  */
 #include <hip/hip_runtime.h>
@@ -161,6 +165,204 @@ void trace_launch_stage2(const TraceArgs& a, hipStream_t st) {
     const int nparts = (a.n + TRACE_PB - 1) / TRACE_PB;
     hipLaunchKernelGGL(k_trace_card, dim3(nparts), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_trace_finish, dim3(3), dim3(256), 0, st, a, nparts);
+}
+
+/* ---- the trace of a sharded step: the record the single context of
+ * N = world * n particles (global index = rank * n + local index) writes, bit
+ * for bit.  The per-particle inputs travel (poses, cardinalities), never
+ * partial sums: the block functions run over all N entries on every rank. ---- */
+
+/* Σ_j w_j of one map by one wave (k_trace_card's sum); sz: its clamped size */
+__device__ __forceinline__ float map_cardinality(const Slab& m, int cap, int lane, int& sz) {
+    sz = min(max(m.size, 0), cap);
+    double s = 0.0;
+    for (int k = lane; k < sz; k += 64) s += (double)m.map[k];
+    s = wave_sum_d(s);
+    return (float)s;
+}
+
+/* Stage 1: k_trace_weights' log-sum-exp, nEff, decision and first arg-max (of
+ * the normalised weights w_all[i] - lse, as expected_pose_block takes it) over
+ * the gathered log-weights. */
+__global__ void __launch_bounds__(RS_THREADS) k_trace_shard_weights(TraceShardArgs a) {
+    __shared__ double s_d[64];
+    __shared__ float s_f[32];
+    const int t = threadIdx.x;
+    const int N = a.world * a.n;
+    float mx = -INFINITY;
+    for (int i = t; i < N; i += RS_THREADS) mx = fmaxf(mx, a.w_all[i]);
+    PHD_BLOCK_MAX_1024(mx, s_f, t & 63, t >> 6);
+    const double sum = chunk_sum_block(N, [&](int i) { return (double)expf(a.w_all[i] - mx); }, s_d);
+    const float lse = d_safe_log((float)sum) + mx;
+    const double s2 = chunk_sum_block(N, [&](int i) { return (double)expf(2 * (a.w_all[i] - lse)); }, s_d + 32);
+    const float neff = neff_of(s2, N);
+    const int resample = resample_decision(neff, a.has_meas, a.resample_thresh);
+    float bw = -FLT_MAX;
+    int bi = INT_MAX;
+    for (int i = t; i < N; i += RS_THREADS) {
+        const float w = a.w_all[i] - lse;
+        if (w > bw) {
+            bw = w;
+            bi = i;
+        }
+    }
+    const int amax = first_argmax_block(bw, bi);
+    if (t == 0) {
+        const int best = amax >= 0 && amax < N ? amax : 0;
+        phd_trace_record r;
+        r.step = a.step;
+        r.n_live = N;
+        r.n_measure = a.M;
+        r.resampled = resample;
+        r.neff = neff;
+        r.expected_pose = phd_pose{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // the finish stage
+        r.map_particle = amax;
+        r.map_pose = phd_pose{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        r.card_expected = 0.f;
+        r.card_map = 0.f;
+        r.map_size = 0;
+        r.status_errors = 0;
+        r.reserved = 0;
+        *a.rec = r;
+        a.hand[TRACE_H_PARTICLE] = best;
+        // (a rank that does not own the particle: any valid reference, its rows are not sent)
+        a.hand[TRACE_H_SLAB] = a.src[best / a.n == a.rank ? best - a.rank * a.n : 0];
+        a.hand[TRACE_H_LSE] = __float_as_int(lse);
+    }
+}
+
+/* Stage 2: this rank's block.  Workgroup b takes local particles b * TRACE_PB
+ * onward, one wave per map at a time; every store runs over consecutive words.
+ * Workgroup 0 also writes the header; the snapshot and the cardinality row are
+ * dealt over the whole grid. */
+__global__ void __launch_bounds__(256) k_trace_shard_pack(TraceShardArgs a) {
+    __shared__ float s_cn[TRACE_PB];
+    __shared__ int s_hdr[TRACE_BH_WORDS];
+    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+    const int base = blockIdx.x * TRACE_PB;
+    const int best = a.hand[TRACE_H_PARTICLE];
+    const bool owner = best / a.n == a.rank;
+    float* pose_o = a.block + TRACE_BH_WORDS;
+    float* cn_o = pose_o + (size_t)6 * a.n;
+    float* snap_o = cn_o + a.n;
+    float* row_o = snap_o + (size_t)PHD_NF * a.snap_cap;
+    for (int q = wid; q < TRACE_PB; q += 4) {
+        const int p = base + q;
+        if (p >= a.n) break;
+        int sz;
+        const float cn = map_cardinality(slab_of(a.src[p], a.map_in, a.size_in, a.map_x, a.size_x, a.cap), a.cap, lane, sz);
+        if (lane == 0) s_cn[q] = cn;
+    }
+    if (blockIdx.x == 0) {
+        if (t < TRACE_BH_WORDS) s_hdr[t] = 0;
+        __syncthreads();
+        if (wid == 0 && owner) {
+            int sz;
+            const float cn =
+                map_cardinality(slab_of(a.hand[TRACE_H_SLAB], a.map_in, a.size_in, a.map_x, a.size_x, a.cap), a.cap, lane, sz);
+            if (lane == 0) {
+                s_hdr[TRACE_BH_OWNER] = 1;
+                s_hdr[TRACE_BH_SIZE] = sz;
+                s_hdr[TRACE_BH_CARD] = __float_as_int(cn);
+            }
+        }
+        if (t == 64) {
+            const int e = a.err[3], prev = a.hand[TRACE_H_ERRPREV];
+            s_hdr[TRACE_BH_ERR] = e >= prev ? e - prev : e;  // (the counter was taken and cleared in between)
+            a.hand[TRACE_H_ERRPREV] = e;
+        }
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && t < TRACE_BH_WORDS) ((int*)a.block)[t] = s_hdr[t];
+    const int np = min(TRACE_PB, a.n - base);
+    if (t < np) cn_o[base + t] = s_cn[t];
+    if (t < 6 * np) pose_o[(size_t)6 * base + t] = ((const float*)a.pose)[(size_t)6 * base + t];
+    // the owner's snapshot (Gaussian2D words, as k_trace_finish) and cardinality row; zeros elsewhere
+    const Slab m = slab_of(a.hand[TRACE_H_SLAB], a.map_in, a.size_in, a.map_x, a.size_x, a.cap);
+    const int rows = owner ? min(min(max(m.size, 0), a.cap), a.snap_cap) : 0;
+    const int stride = gridDim.x * 256, g = blockIdx.x * 256 + t;
+    for (int e = g; e < a.snap_cap * PHD_NF; e += stride) {
+        const int k = e / PHD_NF, j = e - k * PHD_NF;
+        const int f = j < 4 ? 3 + j : j < 6 ? j - 3 : 0;
+        snap_o[e] = k < rows ? m.map[(size_t)f * a.cap + k] : 0.f;
+    }
+    for (int k = g; k < a.K; k += stride) row_o[k] = owner && a.card_row ? a.card_row[k] : 0.f;
+    const int used = TRACE_BH_WORDS + 7 * a.n + PHD_NF * a.snap_cap + a.K;  // (the rounding words)
+    if (blockIdx.x == 0 && used + t < (int)a.block_words) a.block[used + t] = 0.f;
+}
+
+/* Stage 4.  Workgroup 0: the expected pose by expected_pose_block over the N
+ * gathered poses, and the owner's header, the arg-max particle's pose and the
+ * ranks' error counts into the record.  Workgroup 1: card_expected in
+ * k_trace_card / k_trace_finish's order (partials of TRACE_PB consecutive
+ * global indices, term by term; thread t < 256 adds partials t, t + 256, ...;
+ * wave scans; the four wave totals in order), then the owner's snapshot and
+ * cardinality row into this scan's ring entries. */
+__global__ void __launch_bounds__(RS_THREADS) k_trace_shard_finish(TraceShardArgs a) {
+    const int t = threadIdx.x;
+    const int n = a.n, N = a.world * n;
+    const float lse = __int_as_float(a.hand[TRACE_H_LSE]);
+    const int best = a.hand[TRACE_H_PARTICLE];
+    const float* own = a.blocks + (size_t)(best / n) * a.block_words;
+    auto pose_of = [&](int i) {
+        const int r = i / n;
+        return a.blocks + (size_t)r * a.block_words + TRACE_BH_WORDS + (size_t)6 * (i - r * n);
+    };
+    if (blockIdx.x == 0) {
+        __shared__ double s_r[32];
+        float ep[6];
+        expected_pose_block_at(N, [&](int i) { return a.w_all[i] - lse; }, pose_of, ep, s_r);
+        if (t == 0) {
+            const float* mp = pose_of(best);
+            a.rec->expected_pose = phd_pose{ep[0], ep[1], ep[2], ep[3], ep[4], ep[5]};
+            a.rec->map_pose = phd_pose{mp[0], mp[1], mp[2], mp[3], mp[4], mp[5]};
+            a.rec->card_map = own[TRACE_BH_CARD];
+            a.rec->map_size = ((const int*)own)[TRACE_BH_SIZE];
+            int errs = 0;
+            for (int r = 0; r < a.world; r++) errs += ((const int*)(a.blocks + (size_t)r * a.block_words))[TRACE_BH_ERR];
+            a.rec->status_errors = errs;
+        }
+    } else {
+        __shared__ double s_w[4];
+        const int nparts = (N + TRACE_PB - 1) / TRACE_PB;
+        double v = 0.0;
+        if (t < 256)
+            for (int b = t; b < nparts; b += 256) {
+                double s = 0.0;
+                for (int q = 0; q < TRACE_PB; q++) {
+                    const int p = b * TRACE_PB + q;
+                    double term = 0.0;
+                    if (p < N) {
+                        const int r = p / n;
+                        const float cn = a.blocks[(size_t)r * a.block_words + TRACE_BH_WORDS + (size_t)6 * n + (p - r * n)];
+                        term = (double)expf(a.w_all[p] - lse) * (double)cn;
+                    }
+                    s += term;
+                }
+                v += s;
+            }
+        v = wave_incl_scan_d(v);
+        if (t < 256 && (t & 63) == 63) s_w[t >> 6] = v;
+        __syncthreads();
+        if (t == 0) a.rec->card_expected = (float)(((s_w[0] + s_w[1]) + s_w[2]) + s_w[3]);
+        const float* snap_i = own + TRACE_BH_WORDS + (size_t)7 * n;
+        if (a.snap)
+            for (int e = t; e < a.snap_cap * PHD_NF; e += RS_THREADS) ((float*)a.snap)[e] = snap_i[e];
+        if (a.card)
+            for (int k = t; k < a.K; k += RS_THREADS) a.card[k] = snap_i[(size_t)PHD_NF * a.snap_cap + k];
+    }
+}
+
+void trace_launch_shard_weights(const TraceShardArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_trace_shard_weights, dim3(1), dim3(RS_THREADS), 0, st, a);
+}
+
+void trace_launch_shard_pack(const TraceShardArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_trace_shard_pack, dim3((a.n + TRACE_PB - 1) / TRACE_PB), dim3(256), 0, st, a);
+}
+
+void trace_launch_shard_finish(const TraceShardArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_trace_shard_finish, dim3(2), dim3(RS_THREADS), 0, st, a);
 }
 
 }  // namespace phd

@@ -180,6 +180,9 @@ class ShardedFilter:
          destination) packs FIXED blocks of `block_records` records per peer;
       4. one equal-split all_to_all of the blocks (every step: the host never
          learns the decision before it), and the receive into the deficit slots.
+    With enable_trace, between 3's all_gather and its plan: every rank packs its
+    trace block, one all_gather of the blocks, and the scan's record (the one a
+    single context of all world * n particles writes) joins every rank's ring.
     flush() settles the last plan (before reading the store on the host).
     Fix the local filter's update form (set_update_form / set_update_threads)
     before constructing: the plan stream beside part C is set up only for the
@@ -224,6 +227,7 @@ class ShardedFilter:
         # the all-gather and the plan on a second, high-priority stream beside the
         # update's part C (its log-weights are final after the CPHD terms / the
         # split PHD part A: phd_wait_logw); the pack waits for the plan
+        self.trace_block = self.trace_blocks = None  # enable_trace
         self.aux = None
         if overlap and f.update_form():
             self.aux = torch.cuda.Stream(device=device, priority=-1)
@@ -294,6 +298,39 @@ class ShardedFilter:
             self.K, self.ovf_send.data_ptr(), self.ovf_capacity, self.new_logw)
         self._open = True
 
+    def enable_trace(self, capacity, map_snapshot_cap=0, card_dist=False):
+        """The per-scan estimate trace (PHDFilter.enable_trace) on the sharded
+        step: every step() then appends the scan's record to the local filter's
+        ring (read it with f.read_trace / f.trace_count).  capacity 0: off.  Same
+        arguments on every rank."""
+        import ctypes
+        import torch
+        from . import _lib
+        self.trace_block = self.trace_blocks = None
+        if capacity and card_dist and self.f.config.mapEstimate & 2:
+            self.f.enable_trace(0)
+            raise _lib.PHDError(_lib.PHD_E_UNSUPPORTED, "ShardedFilter.enable_trace",
+                                "card_dist with map_estimate & 2: the expected rows are a sequential sum over "
+                                "every rank's particles")
+        self.f.enable_trace(capacity, map_snapshot_cap, card_dist)
+        if not capacity:
+            return
+        nbytes = ctypes.c_size_t()
+        _lib.check(_lib.lib().phd_trace_shard_block_bytes(self.n, int(map_snapshot_cap), self.f.trace_shape()[2],
+                                                          ctypes.byref(nbytes)), "phd_trace_shard_block_bytes")
+        self.trace_block = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        self.trace_blocks = torch.empty(self.world * nbytes.value, dtype=torch.uint8, device=self.device)
+
+    def trace_pack(self, k):
+        """After gather() and the settle, before plan(): this rank's trace block
+        (the poses, cardinalities and arg-max rows of the store the plan remaps)."""
+        self.f.trace_shard_pack(self.w_all.data_ptr(), self.world, self.rank, k, self.trace_block.data_ptr())
+
+    def trace_append(self):
+        """After the all-gather of the trace blocks into trace_blocks, before plan()
+        (which normalises w_all in place)."""
+        self.f.trace_shard_append(self.w_all.data_ptr(), self.trace_blocks.data_ptr(), self.world, self.rank)
+
     def receive(self):
         """After the all-to-all of the blocks into recv_blocks."""
         self.f.shard_receive_blocks(self.recv_blocks.data_ptr(), self.K, self.recv_rec.data_ptr())
@@ -307,6 +344,10 @@ class ShardedFilter:
         self.local_update(control, k)
         prev = self.settle(control, k)
         self.gather()
+        if self.trace_block is not None:
+            self.trace_pack(k)
+            self.comm.all_gather(self.trace_blocks, self.trace_block)
+            self.trace_append()
         self.plan(k)
         self.comm.all_to_all_equal(self.recv_blocks, self.send_blocks)
         self.receive()
@@ -370,6 +411,14 @@ class GroupRank:
         self.last = (ne.value, rs.value) if rs.value >= 0 else (None, None)
         return self.last
 
+    def enable_trace(self, capacity, map_snapshot_cap=0, card_dist=False):
+        """phd_group_trace_enable: as ShardedFilter.enable_trace (records through
+        the local filter's read_trace / trace_count)."""
+        from .types import TRACE_CARD_DIST
+        _group_check(self.L, self.L.phd_group_trace_enable(self._g, int(capacity), int(map_snapshot_cap),
+                                                           TRACE_CARD_DIST if card_dist else 0),
+                     "phd_group_trace_enable")
+
     def flush(self):
         _group_check(self.L, self.L.phd_group_flush(self._g), "phd_group_flush")
 
@@ -409,6 +458,7 @@ def group_lib():
         L.phd_group_step.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_float),
                                      ctypes.POINTER(ctypes.c_int)]
         L.phd_group_flush.argtypes = [vp]
+        L.phd_group_trace_enable.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint]
         L.phd_group_stats.argtypes = [vp, vp]
         L.phd_group_destroy.argtypes = [vp]
         L.phd_group_last_error.restype = ctypes.c_char_p

@@ -274,8 +274,13 @@ class PHDFilter:
         log cardinality distribution."""
         _lib.check(_lib.lib().phd_trace_enable(self._h, int(capacity), int(map_snapshot_cap),
                                                TRACE_CARD_DIST if card_dist else 0), "phd_trace_enable")
-        self._trace = (int(capacity), int(map_snapshot_cap),
-                       self.config.maxCardinality + 1 if card_dist and capacity else 0)
+
+    def trace_shape(self):
+        """phd_trace_shape: (capacity, map_snapshot_cap, floats per cardinality row) of the enabled trace."""
+        c, s, k = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _lib.check(_lib.lib().phd_trace_shape(self._h, ctypes.byref(c), ctypes.byref(s), ctypes.byref(k)),
+                   "phd_trace_shape")
+        return c.value, s.value, k.value
 
     def trace_count(self):
         """Scans appended since enable_trace (no synchronisation)."""
@@ -288,7 +293,7 @@ class PHDFilter:
         scan the ring still holds); with snapshots / cardinality distributions
         enabled returns (records, maps[count, map_snapshot_cap] GAUSSIAN2D or None,
         card[count, max_cardinality + 1] float32 or None).  One synchronisation."""
-        cap, snap, K = getattr(self, "_trace", (0, 0, 0))
+        cap, snap, K = self.trace_shape()
         total = self.trace_count()
         if first is None:
             first = max(0, total - cap)
@@ -459,6 +464,17 @@ class PHDFilter:
         _lib.check(_lib.lib().phd_shard_receive_overflow(self._h, ctypes.c_void_p(dev_ovf_ptr), int(block_records),
                                                          ctypes.c_void_p(dev_recv_rec_ptr)),
                    "phd_shard_receive_overflow")
+
+    def trace_shard_pack(self, dev_w_all_ptr, world, rank, step, dev_block_ptr):
+        """phd_trace_shard_pack: this rank's block of the sharded step's trace."""
+        _lib.check(_lib.lib().phd_trace_shard_pack(self._h, ctypes.c_void_p(dev_w_all_ptr), int(world), int(rank),
+                                                   int(step), ctypes.c_void_p(dev_block_ptr)), "phd_trace_shard_pack")
+
+    def trace_shard_append(self, dev_w_all_ptr, dev_blocks_ptr, world, rank):
+        """phd_trace_shard_append: the scan's record from the gathered blocks."""
+        _lib.check(_lib.lib().phd_trace_shard_append(self._h, ctypes.c_void_p(dev_w_all_ptr),
+                                                     ctypes.c_void_p(dev_blocks_ptr), int(world), int(rank)),
+                   "phd_trace_shard_append")
 
     def update_pending(self, control, step, dev_logw_out_ptr=None, do_predict=True):
         u = ctypes.byref(AckermanControl(float(control[1]), float(control[0]))) if control is not None else None

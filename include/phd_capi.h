@@ -309,7 +309,8 @@ int phd_expected_map_groups(phd_ctx* ctx, int* groups);
  * the arg-max particle's row of phd_export_maps) at the point of the reference's
  * loop where recoverSlamState takes them — after the normalisation, before the
  * resample — computed by kernels on the context's stream (phd_trace.hip) with
- * no host synchronisation.  Only phd_step appends; phd_predict_update,
+ * no host synchronisation.  phd_step appends, and a sharded step through
+ * phd_trace_shard_pack / phd_trace_shard_append (below); phd_predict_update,
  * phd_normalize and phd_resample never do.  A traced step runs its resample
  * after the update (not beside part C): the trace reads the poses and
  * log-weights the resample rewrites.
@@ -323,10 +324,11 @@ int phd_expected_map_groups(phd_ctx* ctx, int* groups);
  * combination Σ_n exp(w_n) cn_n[k] recoverSlamState makes, else the arg-max
  * particle's (zeros until a CPHD update has run).  capacity 0 turns the trace
  * off and frees the rings; enabling again restarts the count at 0.
- * PHD_E_UNSUPPORTED: feature_model 2, n_predict_particles > 1, a context that
- * holds migrated (sharded) slabs, PHD_TRACE_CARD_DIST without CPHD.  Needs
- * phd_set_config first.  Replay mode is supported (every record is the same).
- * Synchronises (an allocation, not a step). */
+ * PHD_E_UNSUPPORTED: feature_model 2, n_predict_particles > 1,
+ * PHD_TRACE_CARD_DIST without CPHD; and from a traced phd_step on a context
+ * that holds migrated (sharded) slabs.  Needs phd_set_config first.  Replay
+ * mode is supported (every record is the same).  Synchronises (an allocation,
+ * not a step). */
 #define PHD_TRACE_CARD_DIST 1
 int phd_trace_enable(phd_ctx* ctx, int capacity, int map_snapshot_cap, unsigned flags);
 /* Records appended since phd_trace_enable (the host's count: no synchronisation). */
@@ -337,6 +339,44 @@ int phd_trace_count(phd_ctx* ctx, long* written_total);
  * PHD_E_ARG if part of the range has been overwritten or not written yet. */
 int phd_trace_read(phd_ctx* ctx, long first, int count, phd_trace_record* records, phd_gaussian2d* maps,
                    float* card);
+/* The enabled trace: ring capacity (0: off), snapshot components per scan and
+ * floats per cardinality row (0 without PHD_TRACE_CARD_DIST). */
+int phd_trace_shape(phd_ctx* ctx, int* capacity, int* map_snapshot_cap, int* card_k);
+
+/* ---- the trace of a sharded step ----
+ * With the trace on (phd_trace_enable on every rank's context, same arguments),
+ * a sharded step appends to every rank's ring the record the single context of
+ * N = world * n particles (global index = rank * n + local index) would write
+ * for the scan, bit for bit: n_live = N, map_particle a global index, the map
+ * fields from the rank that owns that particle, status_errors the sum over the
+ * ranks of each one's count since its previous traced step.  The sums of the
+ * single context do not split into per-rank partial sums, so the per-particle
+ * inputs travel: every rank packs a fixed-size block (header | n poses | n
+ * cardinalities | the arg-max particle's snapshot and cardinality row, zero
+ * unless the rank owns it: phd_trace_shard_block_bytes, 64 + 28 n + 28
+ * map_snapshot_cap + 4 K bytes rounded up to 16, K = phd_trace_shape's card_k),
+ * the caller all-gathers the blocks (rank order), and every rank finishes the
+ * record from the gathered blocks.  Per step the caller makes, between the
+ * all-gather of the log-weights and phd_shard_resample_async:
+ *     phd_predict_update; phd_shard_poll .. phd_update_pending (the settle);
+ *     all-gather of the log-weights into dev_w_all;
+ *     phd_trace_shard_pack(ctx, dev_w_all, world, rank, step, dev_block);
+ *     all-gather of dev_block into dev_blocks_all, on the context stream;
+ *     phd_trace_shard_append(ctx, dev_w_all, dev_blocks_all, world, rank);
+ *     phd_shard_resample_async(..)   -- normalises dev_w_all in place, remaps
+ * The pack reads the poses, slab references and posterior maps of this step:
+ * after the update and any pending-slot re-update, before the plan's remap.
+ * Both calls enqueue on the context stream and wait for nothing on the host;
+ * with a plan stream set (phd_set_plan_stream) the pack first orders the
+ * context stream after the caller's all-gather there, and the plan of a traced
+ * step runs after the append, not beside part C.  phd_trace_count / _read
+ * serve any rank's context; phd_trace_shard_append advances the count.
+ * PHD_E_UNSUPPORTED: what phd_trace_enable refuses, and PHD_TRACE_CARD_DIST
+ * with map_estimate & 2 (the expected rows are a sequential float sum over
+ * every rank's particles).  world * n <= 2^20 as phd_shard_resample_async. */
+int phd_trace_shard_block_bytes(int n, int map_snapshot_cap, int K, size_t* bytes);
+int phd_trace_shard_pack(phd_ctx* ctx, const float* dev_w_all, int world, int rank, uint64_t step, void* dev_block);
+int phd_trace_shard_append(phd_ctx* ctx, const float* dev_w_all, const void* dev_blocks_all, int world, int rank);
 
 /* Per-update timing of the fused kernel with HIP events recorded on the
  * context stream around each launch (ring of max_records pairs).

@@ -10,6 +10,8 @@
  *        blocks go point to point (grouped ncclSend / ncclRecv), then
  *        phd_shard_receive_overflow + phd_update_pending on the slots they feed
  *     3. ncclAllGather of the n log-weights (grouped over the ranks)
+ *     3t. (phd_group_trace_enable) phd_trace_shard_pack, ncclAllGather of the
+ *        trace blocks, phd_trace_shard_append: the scan's estimate record
  *     4. phd_shard_resample_async (global normalise / nEff / decision /
  *        parents, identical on every rank; plan; fixed blocks packed)
  *     5. equal-split all-to-all of the blocks (grouped ncclSend / ncclRecv)
@@ -62,6 +64,14 @@ int phd_group_destroy(phd_group* g);
  * work enqueued; *neff / *resampled (optional) receive the PREVIOUS step's plan
  * (its counts are polled here), 0 / -1 on the first step. */
 int phd_group_step(phd_group* g, const phd_ackerman_control* u, uint64_t step, float* neff, int* resampled);
+/* The per-scan estimate trace (phd_trace_enable, phd_capi.h) on the sharded
+ * step: enables it on every context of the group with these arguments
+ * (capacity 0: off) and allocates the trace blocks.  Every phd_group_step then
+ * appends the scan's record — the one a single context of all world * n
+ * particles writes — to every rank's ring: read it with phd_trace_read /
+ * phd_trace_count on any rank's context.  A traced step runs its plan after
+ * the trace instead of beside part C.  Synchronises (an allocation). */
+int phd_group_trace_enable(phd_group* g, int capacity, int map_snapshot_cap, unsigned flags);
 /* Settle the last plan (no update follows): the contexts' stores are final. */
 int phd_group_flush(phd_group* g);
 /* Counters over the steps so far: [0] resamples, [1] migrated particles,

@@ -11,7 +11,9 @@ kernels, block exchange copies), i.e. what the collectives add to on top on a
 real node.  `--skew s` offsets rank r's gathered log-weights by r * s, so the
 plan migrates particles (this rank, the lightest, receives: records arrive in
 the blocks and, beyond them, through the overflow exchange and a re-update of
-the pending slots).  `host_wait_us` is the time step() spends waiting for the device per
+the pending slots).  `--trace` turns the estimate trace on (ShardedFilter.
+enable_trace: pack, the blocks' all-gather as a local copy, append; every rank
+slot then holds this rank's block).  `host_wait_us` is the time step() spends waiting for the device per
 step: the only wait is phd_shard_poll on the PREVIOUS step's plan while the
 current update runs, so the device queue never drains (`gpu_idle_us`: sharded
 step time minus the device time of its kernels ≈ 0).  Diagnostic.
@@ -39,7 +41,7 @@ class LocalComm:
     def all_gather(self, out, inp):
         v = out.view(self.world, -1)
         v.copy_(inp.view(1, -1).expand(self.world, -1))
-        if self.skew:
+        if self.skew and v.is_floating_point():  # (the log-weights, not the trace blocks)
             import torch
             v += self.skew * torch.arange(self.world, device=v.device, dtype=v.dtype).view(-1, 1)
 
@@ -60,6 +62,7 @@ def main():
     ap.add_argument("--particles", type=int, default=0, help="particles per rank (default: the config's per GPU)")
     ap.add_argument("--skew", type=float, default=0.0,
                     help="log-weight offset per rank slot: > 0 makes the plan migrate particles")
+    ap.add_argument("--trace", action="store_true", help="the sharded step with the estimate trace on")
     a = ap.parse_args()
     import torch
     import phdslam
@@ -100,6 +103,8 @@ def main():
     f.close()
     f = make()
     sh = ShardedFilter(f, None, dev, world=a.world, rank=0, comm=LocalComm(a.world, a.skew))
+    if a.trace:
+        sh.enable_trace(a.steps + 20)
     for k in range(20):
         sh.step(control if motion_ack else None, k)
     sh.flush()
@@ -131,6 +136,10 @@ def main():
     res["world"] = a.world
     res["config"] = a.config
     res["skew"] = a.skew
+    res["trace"] = a.trace
+    if a.trace:
+        assert f.trace_count() == a.steps + 20
+        res["trace_block_bytes"] = sh.trace_block.numel()
     for k in ("migrated", "records", "overflow_records", "pending_slots"):
         if k in sh.stats:
             res[k + "_per_step"] = round(sh.stats[k] / (a.steps + 20), 1)
