@@ -7,6 +7,12 @@ itself decided within MARGIN (1e-4 relative) of a threshold: such prune / merge
 decisions may change only the components they touch (the rest of the particle
 is still compared), a near range classification skips the particle (counted,
 bounded).  Resample indices are bit-exact.
+
+The oracle shares include/phd_detmath.h and several statements of the
+arithmetic with the kernels (oracle/scphd_cpu.cpp, D14, D16-D18); the bound
+that does not depend on it is tests/test_gpu_ref64.py: the device against the
+float64 reference tests/update_ref64.py, at the oracle's measured distance from
+that reference plus this contract.
 """
 import os
 
@@ -32,7 +38,7 @@ def _filter(cfg, n, **cap):
 
 
 def _check_update(cfg, poses, lw, maps, offs, z, label, max_skip_frac=0.02, threads=0, sample=None, form=0,
-                  with_form=False, rtol=parity.RTOL, births=False, elementwise=False, **cap):
+                  with_form=False, rtol=parity.RTOL, births=False, elementwise=False, normalised=False, **cap):
     """Update through the C-ABI vs the oracle.  Particles without near-threshold
     decisions are compared whole (map multiset, log-weight).  Particles whose
     oracle has prune / merge decisions within MARGIN of their threshold are still
@@ -48,7 +54,8 @@ def _check_update(cfg, poses, lw, maps, offs, z, label, max_skip_frac=0.02, thre
     before the update, phd_set_step_births) — run as the bench runs them (replay,
     phd_predict_update without a predict) against the oracle's add_births ->
     update.  elementwise: assert SURVEY §8(d)'s per-element measure on every
-    entry that is not a cancellation entry (_compare_with_oracle)."""
+    entry that is not a cancellation entry (_compare_with_oracle).  normalised:
+    assert the log-weights in SURVEY §8(d)'s form too (_compare_with_oracle)."""
     n = len(poses)
     f = _filter(cfg, n, **cap)
     if form:
@@ -72,7 +79,7 @@ def _check_update(cfg, poses, lw, maps, offs, z, label, max_skip_frac=0.02, thre
     if births:
         maps, offs = pyoracle.add_births(cfg, poses, maps, offs, z)
     worst, compared = _compare_with_oracle(cfg, poses, lw, maps, offs, z, (glw, gmaps, goffs), label, max_skip_frac,
-                                           sample, rtol, elementwise)
+                                           sample, rtol, elementwise, normalised)
     # poses untouched by the update
     assert gp.tobytes() == np.ascontiguousarray(poses, POSE).tobytes()
     if with_form:
@@ -105,8 +112,11 @@ def _record_elementwise(entry):
 
 
 def _compare_with_oracle(cfg, poses, lw, maps, offs, z, gpu, label, max_skip_frac=0.02, sample=None,
-                         rtol=parity.RTOL, elementwise=False):
-    """elementwise: besides the scaled contract (parity.compare_maps), every
+                         rtol=parity.RTOL, elementwise=False, normalised=False):
+    """normalised: besides the assertion scaled by the addends, SURVEY §8(d)'s
+    form: the log-weights of the particles compared, normalised by their
+    logsumexp on both sides, within 1e-5 relative with a 1e-5 absolute floor.
+    elementwise: besides the scaled contract (parity.compare_maps), every
     entry that is not a cancellation entry (weights, covariance diagonals, mean
     coordinates with |x| >= 1; parity.noncancellation_mask) must meet SURVEY
     §8(d)'s per-element |a - b| <= 1e-5 max(|a|, |b|) itself.  The figures of
@@ -152,12 +162,22 @@ def _compare_with_oracle(cfg, poses, lw, maps, offs, z, gpu, label, max_skip_fra
     g = glw[sample]
     lref = np.maximum(np.abs(g[~skip]).astype(np.float64), np.abs(ow[~skip]).astype(np.float64))
     ldev = np.abs(g[~skip].astype(np.float64) - ow[~skip].astype(np.float64))
+    from scipy.special import logsumexp
+    gk, okk = g[~skip].astype(np.float64), ow[~skip].astype(np.float64)
+    gn, on = gk - logsumexp(gk), okk - logsumexp(okk)
+    ndev = np.abs(gn - on)
+    nlim = 1e-5 * np.maximum(np.abs(gn), np.abs(on)) + 1e-5
+    print(f"{label}: normalised log-weights: worst |a-b| {ndev.max():.3g} "
+          f"({int(np.sum(ndev > nlim))} of {ndev.size} beyond 1e-5 max(|a|,|b|) + 1e-5; worst excess ratio "
+          f"{float(np.max(ndev / nlim)):.3g})")
     _record_elementwise(dict(label=label, particles=int(ns), compared=int(compared), skipped=int(skip.sum()),
                              near_prune_merge=int(np.sum(npm > 0)), contract_worst=float(worst), rtol=float(rtol),
                              elem_worst=float(strict[0]), elem_beyond=int(strict[1]), elements=int(strict[2]),
                              noncancel_beyond=int(strict[3]), noncancel_worst=float(strict[4]),
                              logw_elem_worst=float(np.max(ldev / np.maximum(lref, 1e-30))) if ldev.size else 0.0,
-                             logw_elem_beyond=int(np.sum(ldev > 1e-5 * lref + 1e-30)), elementwise_asserted=elementwise))
+                             logw_elem_beyond=int(np.sum(ldev > 1e-5 * lref + 1e-30)), elementwise_asserted=elementwise,
+                             lognorm_worst_abs=float(ndev.max()), lognorm_beyond=int(np.sum(ndev > nlim)),
+                             lognorm_worst_ratio=float(np.max(ndev / nlim)), lognorm_asserted=normalised))
     assert not bad, f"{label}: {bad[:5]}"
     if elementwise:
         assert strict[3] == 0, (f"{label}: {strict[3]} weights / covariance diagonals / means with |x| >= 1 beyond "
@@ -168,6 +188,9 @@ def _compare_with_oracle(cfg, poses, lw, maps, offs, z, gpu, label, max_skip_fra
     mag = np.maximum(np.abs(slw), np.abs(odelta))
     ok = parity.close(g[~skip], ow[~skip], 1e-5, floor=1e-5, scale=mag[~skip])
     assert ok.all(), f"{label}: log-weight mismatch max {np.max(np.abs(g - ow))}"
+    if normalised:
+        assert (ndev <= nlim).all(), (f"{label}: {int(np.sum(ndev > nlim))} normalised log-weights beyond 1e-5 relative "
+                                      f"+ 1e-5 (worst |a-b| {ndev.max():.3g})")
     return worst, compared
 
 
@@ -293,7 +316,7 @@ def test_cphd_update_bench_configuration_every_particle(gpu):
     cap = bench_capacities(3, G, M)
     pyoracle.set_threads(int(os.environ.get("OMP_NUM_THREADS", "16")))
     _, compared, ut = _check_update(c, poses, lw, maps, offs, z, "bench config 3 (every particle)", births=True,
-                                    elementwise=True, **cap)
+                                    elementwise=True, normalised=True, **cap)
     assert ut[0] == 256, f"update instance {ut}"
     assert compared >= n - max(2, int(0.02 * n)), f"{compared} of {n} compared"
 
@@ -324,7 +347,7 @@ def test_phd_update_bench_configuration(gpu, cid, n, nt, split, every, rtol):
     sample = np.arange(0, n, every)
     pyoracle.set_threads(int(os.environ.get("OMP_NUM_THREADS", "16")))
     _, compared, ut, form = _check_update(c, poses, lw, maps, offs, z, f"bench config {cid}", sample=sample,
-                                          with_form=True, rtol=rtol, elementwise=True, **cap)
+                                          with_form=True, rtol=rtol, elementwise=True, normalised=True, **cap)
     if nt is not None:  # (configs 2 / 4: whichever the occupancy model picks — bench.py runs the same choice)
         assert ut[0] == nt and form == split, f"update instance {ut}, split {form}"
     assert compared >= 0.98 * len(sample) and len(sample) >= 32
