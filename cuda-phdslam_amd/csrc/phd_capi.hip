@@ -145,6 +145,7 @@ struct phd_ctx {
         RsStepArgs a;
         int B = 0;
     } rs_ov;
+    int rs_form = 0;  // PHD_RS_FORM_*: what the last phd_step launched (phd_last_resample_form)
     hipStream_t aux = nullptr;
     hipEvent_t ev_terms = nullptr, ev_rs = nullptr;
     // the sharded step beside part C (phd_wait_logw / phd_set_plan_stream):
@@ -1496,6 +1497,9 @@ static int launch_update(phd_ctx* ctx, const FusedPredict* fused = nullptr, cons
     // indexes its records by workgroup: it keeps the second stream.)
     auto rs_lead = [&](UpdateArgs& x) -> int {
         if (!PHD_RS_LEAD || !ctx->rs_ov.armed || slots || x.stamps) return 0;
+        // (part C's LDS must hold rs_step_block's tables: with small capacities
+        // it does not, and the resample takes the second stream instead)
+        if ((size_t)ctx->upd_lds < rs_step_lds(ctx->upd_threads)) return 0;
         x.rs_lead = RS_LEAD_WGS;
         x.rs = ctx->rs_ov.a;
         ctx->rs_ov.launched = true;
@@ -2288,19 +2292,23 @@ int phd_step(phd_ctx* ctx, const phd_ackerman_control* u, int do_predict, uint64
         int f;
         memcpy(&f, &out[2], sizeof(int));
         if (f) ctx->n = ctx->n_base;
+        ctx->rs_form = PHD_RS_FORM_SEPARATE;
         if (neff_out) *neff_out = out[1];
         if (resampled) *resampled = f;
         return PHD_OK;
     }
     if (ctx->n <= 2 * RS_THREADS) {  // one launch: a single block is fastest here
+        ctx->rs_form = PHD_RS_FORM_BLOCK;
         hipLaunchKernelGGL(k_normalize_resample, dim3(1), dim3(1024), rs_lds(ctx->n), ctx->stream, ctx->d_logw,
                            ctx->n, ctx->d_out, cfg.resampleThresh, ctx->M > 0 ? 1 : 0, ctx->seed, step, ctx->d_cdf,
                            ctx->d_idx, ctx->d_pose, ctx->d_src, ctx->d_tmp_pose, ctx->d_tmp_src, neglogn);
         HIPCHK(hipGetLastError());
     } else {  // chunked over n/1024 workgroups; the search writes the remap into the spare arrays
         if (ov_done) {
+            ctx->rs_form = ov_launched ? PHD_RS_FORM_BESIDE : PHD_RS_FORM_LEAD;
             if (ov_launched) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_rs, 0));  // (ran beside part C)
         } else {
+            ctx->rs_form = fuse_max ? PHD_RS_FORM_STEP : PHD_RS_FORM_CHUNKS;  // (launch_rs_chunks: fused up to 16 chunks)
             rc = launch_rs_chunks(ctx, ctx->d_logw, ctx->n, ctx->d_out, ctx->seed, step, ctx->d_idx, true, neglogn,
                                   fuse_max);
             if (rc) return rc;
@@ -2767,6 +2775,12 @@ int phd_resample_count(phd_ctx* ctx, int* count) {
     HIPCHK(hipMemcpyAsync(&c[1], ctx->d_out + 44, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     *count = (int)(c[0] + c[1]);
+    return PHD_OK;
+}
+
+int phd_last_resample_form(phd_ctx* ctx, int* form) {
+    if (!ctx || !form) return fail(PHD_E_ARG, "null argument");
+    *form = ctx->rs_form;
     return PHD_OK;
 }
 

@@ -75,6 +75,14 @@ struct RsStepArgs {
  * their XCD (upd_particle) and no second stream or cross-stream event sits on
  * the step's critical path */
 #define RS_LEAD_WGS 8
+/* dynamic LDS rs_step_block<NT> takes from the part C allocation: four [16][16]
+ * tables of 8-byte words, 16 chunk ends, NT/64 + 1 floats, two ints.  A part C
+ * launch with less (small capacities) cannot host the lead workgroup: beyond
+ * the allocation LDS reads return 0 and writes are dropped, so the step would
+ * decide on zeros and leave the log-weights as the update wrote them. */
+__host__ __device__ constexpr size_t rs_step_lds(int nt) {
+    return 4 * 16 * 16 * 8 + 16 * 8 + (size_t)(nt / 64 + 1) * 4 + 2 * 4;
+}
 
 struct UpdateArgs {
     int n, cap, M, Mcap, Kcap, Scap;

@@ -20,6 +20,9 @@ PHD_E_CAPACITY = -3
 PHD_E_UNSUPPORTED = -4
 PHD_E_NODEVICE = -5
 
+# phd_last_resample_form (PHD_RS_FORM_* of include/phd_capi.h)
+RS_FORMS = {0: "none", 1: "block", 2: "step", 3: "chunks", 4: "beside", 5: "lead", 6: "separate"}
+
 _c_int_p = ctypes.POINTER(ctypes.c_int)
 _c_float_p = ctypes.POINTER(ctypes.c_float)
 _vp = ctypes.c_void_p
@@ -57,6 +60,7 @@ SIGNATURES = {
     "phd_resample": (ctypes.c_int, [_vp, _vp, _u64, _vp]),
     "phd_step": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _u64, _c_float_p, _c_int_p]),
     "phd_resample_count": (ctypes.c_int, [_vp, _c_int_p]),
+    "phd_last_resample_form": (ctypes.c_int, [_vp, _c_int_p]),
     "phd_cardinality_distribution": (ctypes.c_int, [_vp, _vp]),
     "phd_predict_update": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _u64, _vp]),
     "phd_copy_log_weights": (ctypes.c_int, [_vp, _vp]),

@@ -266,6 +266,14 @@ class PHDFilter:
                                        ctypes.byref(rs)), "phd_step")
         return neff.value, bool(rs.value)
 
+    def last_resample_form(self):
+        """Device form of the last step()'s normalise / resample: one of
+        _lib.RS_FORMS' names ("block", "step", "chunks", "beside", "lead",
+        "separate"; "none" before the first step)."""
+        c = ctypes.c_int()
+        _lib.check(_lib.lib().phd_last_resample_form(self._h, ctypes.byref(c)), "phd_last_resample_form")
+        return _lib.RS_FORMS[c.value]
+
     # -- per-scan estimate trace on the device ----------------------------
     def enable_trace(self, capacity, map_snapshot_cap=0, card_dist=False):
         """phd_trace_enable: every step() appends one TRACE_RECORD to a device ring

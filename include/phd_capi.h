@@ -148,6 +148,18 @@ int phd_resample(phd_ctx* ctx, const double* u_host, uint64_t step, int* idx_hos
  * resample when nEff <= resample_threshold.  *resampled (optional) reports it. */
 int phd_step(phd_ctx* ctx, const phd_ackerman_control* u, int do_predict, uint64_t step, float* neff_out,
              int* resampled);
+/* Device form of the last phd_step's normalise / nEff / decision / resample
+ * (a host-side record of what phd_step launched; it changes no launch and does
+ * not synchronise).  The forms compute the same bits; tests use this to show
+ * that the form they mean to check is the one that ran. */
+#define PHD_RS_FORM_NONE 0     /* no phd_step yet */
+#define PHD_RS_FORM_BLOCK 1    /* one workgroup, one launch (n <= 2048) */
+#define PHD_RS_FORM_STEP 2     /* one launch, one workgroup per 1024 entries, on the context's stream */
+#define PHD_RS_FORM_CHUNKS 3   /* four launches (more than 16 chunks) */
+#define PHD_RS_FORM_BESIDE 4   /* the one-launch form on a second stream beside part C */
+#define PHD_RS_FORM_LEAD 5     /* one lead workgroup of the part C launch */
+#define PHD_RS_FORM_SEPARATE 6 /* normalise and resample kernels (live count above n_particles) */
+int phd_last_resample_form(phd_ctx* ctx, int* form);
 /* CPHD (filter_type 1): log cardinality distribution of every particle after
  * the last update, cn_host[n * (max_cardinality+1) + k] = log p_n(k)
  * (particles.cardinalities, phdfilter.cu.bak:2700-2706).  Synchronises. */

@@ -13,7 +13,7 @@
  *   2. converts each term to unsigned 64-bit fixed point (scale 2^40) so the
  *      CDF is an exact, order-independent integer prefix sum.
  * The faithful double-CDF walk is kept in the oracle and the two are compared
- * in tests (tests/test_oracle_resample.py).
+ * in tests (tests/test_oracle_closed_form.py).
  */
 #ifndef PHD_DETMATH_H
 #define PHD_DETMATH_H

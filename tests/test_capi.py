@@ -66,6 +66,20 @@ def test_error_codes_without_context(built):
     assert b"null" in L.phd_last_error()
 
 
+def test_last_resample_form_binding(built):
+    """phd_last_resample_form: null arguments are refused, and the binding names
+    every PHD_RS_FORM_* value of the header."""
+    import phdslam
+    from phdslam._lib import RS_FORMS
+    L = phdslam.lib()
+    form = ctypes.c_int(-1)
+    assert L.phd_last_resample_form(None, ctypes.byref(form)) == phdslam._lib.PHD_E_ARG
+    assert form.value == -1
+    txt = open(os.path.join(REPO, "include", "phd_capi.h")).read()
+    declared = {int(v): k.lower() for k, v in re.findall(r"#define PHD_RS_FORM_([A-Z]+) (\d+)", txt)}
+    assert declared == RS_FORMS and len(declared) == 7
+
+
 def test_config_defaults_match_loadconfig(built):
     import phdslam
     c = phdslam.default_config()
