@@ -23,6 +23,7 @@
 #include "phd_capi.h"
 #include "phd_kernels.h"
 #include "phd_slab.h"
+#include "phd_step_plan.h"
 #include "phd_mixed_k.h"
 #include "phd_trace.h"
 
@@ -99,6 +100,7 @@ struct phd_ctx {
     int upd_resident_p = 0;  // the same for the launch that carries a fused predict (its own registers)
     int epool = 0;
     int upd_cphd = 0;            // launch configured for the CPHD kernels
+    std::string upd_cfg_error;   // phd_set_config could not size the launch for its filter / metric (updates report it)
     int upd_split = 0;           // the update runs as part A + part C (CPHD: always, with the terms between)
     int upd_form_req = 0;        // PHD form requested: 0 automatic, 1 fused, 2 split (phd_set_update_form)
     int epool_req = 0;           // merge edge pool requested (phd_set_edge_pool; 0: the occupancy model's)
@@ -137,15 +139,9 @@ struct phd_ctx {
     size_t rsx_bytes = 0;
     unsigned* d_plan_sync = nullptr;  // k_shard_plan's hand-off words (PLAN_*), zero between launches
     float* logw_mirror = nullptr;     // the next full update also writes its log-weights here (phd_predict_update)
-    // PHD_RS_OVERLAP: the resample k_rs_step of this phd_step, launched by the
-    // CPHD chain on `aux` after the terms (its arguments; `launched` once done)
-    struct {
-        bool armed = false, launched = false;
-        bool lead = false;  // (PHD_RS_LEAD) it ran in part C's lead workgroup: no event to wait on
-        RsStepArgs a;
-        int B = 0;
-    } rs_ov;
     int rs_form = 0;  // PHD_RS_FORM_*: what the last phd_step launched (phd_last_resample_form)
+    // PHD_RS_FORM_BESIDE: the step's k_rs_step runs on `aux` beside part C, after
+    // ev_terms (the log-weights final); ev_rs orders the context stream after it
     hipStream_t aux = nullptr;
     hipEvent_t ev_terms = nullptr, ev_rs = nullptr;
     // the sharded step beside part C (phd_wait_logw / phd_set_plan_stream):
@@ -154,7 +150,6 @@ struct phd_ctx {
     // and ev_plan orders the pack after it
     hipEvent_t ev_logw = nullptr, ev_plan = nullptr;
     hipStream_t plan_stream = nullptr;
-    bool logw_marked = false;  // ev_logw recorded since the last phd_wait_logw-relevant update
     bool src_fresh = false;    // every slab reference is the identity (a full update since the last remap)
     int plan_max_blocks = 0;          // workgroups of k_shard_plan resident at once (0: not queried)
     // per-update kernel timing (HIP events on the context stream)
@@ -220,14 +215,6 @@ static int set_device(phd_ctx* c) {
 
 static int launch_predict_dynamic(phd_ctx* ctx);
 
-/* Normalise + nEff + decision + stratified parents of n log-weights (in place)
- * on ceil(n/1024) workgroups: k_rs_max, k_rs_sum, k_rs_cdf, k_rs_search (the
- * multi-block form of k_normalize_resample, same results bit for bit).  out:
- * [0] lse, [1] nEff, [2] decision, [4] decisions counter; parents written only
- * when the decision is 1.  With `remap`, k_rs_search also writes the remapped
- * poses / slab references of its strata into the spare arrays (the identity
- * without a resample) and the new log-weight.  Stream-ordered, no host
- * synchronisation. */
 /* CPHD cardinality coefficients (allocated with the first CPHD use): one row
  * per slab, written by the update of the particle whose posterior slab it is. */
 static int ensure_cn(phd_ctx* c) {
@@ -291,70 +278,78 @@ static int ensure_sync(phd_ctx* ctx) {
     return PHD_OK;
 }
 
-static int launch_rs_chunks(phd_ctx* ctx, float* w, int n, float* out, uint64_t seed, uint64_t step, int* parents,
-                            bool remap = false, float new_logw = 0.f, bool fused_max = false,
-                            unsigned* beyond = nullptr) {
-    const int B = (n + RS_THREADS - 1) / RS_THREADS;
+/* The arguments of k_rs_step, phd_step's one-launch resample over n <= 16
+ * chunks: every block takes the max and all chunk sums itself, the normalised
+ * weights go out of place to d_tmp_logw until the search moves them.  Launches
+ * nothing (the hand-off words' first zeroing apart, on the context stream): the
+ * caller does, on its stream, beside part C or in part C's lead workgroup. */
+static int rs_step_args(phd_ctx* ctx, float* w, int n, float* out, uint64_t seed, uint64_t step, int* parents,
+                        float new_logw, RsStepArgs& a) {
     RsParts P;
     int rc = rs_parts(ctx, n, P);
     if (rc) return rc;
-    unsigned long long* cdf_rel = P.cdf_rel;
-    double* part_sum = P.part_sum;
-    double* part_s2 = P.part_s2;
-    unsigned long long* part_tot = P.part_tot;
-    unsigned long long* part_key = P.part_key;
-    float* part_max = P.part_max;
-    const int has_meas = ctx->M > 0 ? 1 : 0;
-    // fused (phd_step, up to 16 chunks): one k_rs_sumcdf launch (every block
-    // takes the max and all chunk sums itself), the normalised weights out of
-    // place in d_tmp_logw until k_rs_search moves them
-    const bool fused = fused_max && remap && B <= 16;
-    if (fused) {  // one launch: k_rs_step (<= 16 workgroups, always resident at once)
-        if (ensure_sync(ctx)) return PHD_E_HIP;
-        RsStepArgs a{};
-        a.w = w;
-        a.w_out = ctx->d_tmp_logw;
-        a.N = n;
-        a.B = B;
-        a.has_meas = has_meas;
-        a.resample_thresh = ctx->cfg.resampleThresh;
-        a.new_logw = new_logw;
-        a.seed = seed;
-        a.step = step;
-        a.part_s2 = part_s2;
-        a.cdf_rel = cdf_rel;
-        a.part_tot = part_tot;
-        a.part_key = part_key;
-        a.sync = ctx->d_plan_sync;
-        a.out = out;
-        a.parents = parents;
-        a.pose = ctx->d_pose;
-        a.src = ctx->d_src;
-        a.new_pose = ctx->d_tmp_pose;
-        a.new_src = ctx->d_tmp_src;
-        a.logw = w;
-        a.err = ctx->d_err;
-        if (ctx->rs_ov.armed) {  // (PHD_RS_OVERLAP) the update chain launches it beside part C
-            a.src = nullptr;      // the update resets the slab references to the identity
-            ctx->rs_ov.a = a;
-            ctx->rs_ov.B = B;
-            return PHD_OK;
-        }
-        hipLaunchKernelGGL(k_rs_step, dim3(B), dim3(RS_THREADS), 0, ctx->stream, a);
+    if (ensure_sync(ctx)) return PHD_E_HIP;
+    a = RsStepArgs{};
+    a.w = w;
+    a.w_out = ctx->d_tmp_logw;
+    a.N = n;
+    a.B = (n + RS_THREADS - 1) / RS_THREADS;
+    a.has_meas = ctx->M > 0 ? 1 : 0;
+    a.resample_thresh = ctx->cfg.resampleThresh;
+    a.new_logw = new_logw;
+    a.seed = seed;
+    a.step = step;
+    a.part_s2 = P.part_s2;
+    a.cdf_rel = P.cdf_rel;
+    a.part_tot = P.part_tot;
+    a.part_key = P.part_key;
+    a.sync = ctx->d_plan_sync;
+    a.out = out;
+    a.parents = parents;
+    a.pose = ctx->d_pose;
+    a.src = ctx->d_src;
+    a.new_pose = ctx->d_tmp_pose;
+    a.new_src = ctx->d_tmp_src;
+    a.logw = w;
+    a.err = ctx->d_err;
+    return PHD_OK;
+}
+
+/* Normalise + nEff + decision + stratified parents of n log-weights (in place)
+ * on ceil(n/1024) workgroups of stream st: k_rs_max, k_rs_sum, k_rs_cdf,
+ * k_rs_search (the multi-block form of k_normalize_resample, same results bit
+ * for bit).  out: [0] lse, [1] nEff, [2] decision, [4] decisions counter;
+ * parents written only when the decision is 1.  With `remap`, k_rs_search also
+ * writes the remapped poses / slab references of its strata into the spare
+ * arrays (the identity without a resample) and the new log-weight; with
+ * `fused_max` too and up to 16 chunks it is one k_rs_step launch (<= 16
+ * workgroups, always resident at once).  Stream-ordered, no host
+ * synchronisation. */
+static int launch_rs_chunks(phd_ctx* ctx, hipStream_t st, float* w, int n, float* out, uint64_t seed, uint64_t step,
+                            int* parents, bool remap = false, float new_logw = 0.f, bool fused_max = false,
+                            unsigned* beyond = nullptr) {
+    const int B = (n + RS_THREADS - 1) / RS_THREADS;
+    if (fused_max && remap && B <= 16) {
+        RsStepArgs a;
+        int rc = rs_step_args(ctx, w, n, out, seed, step, parents, new_logw, a);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_rs_step, dim3(B), dim3(RS_THREADS), 0, st, a);
         HIPCHK(hipGetLastError());
         return PHD_OK;
-    } else {
-        hipLaunchKernelGGL(k_rs_max, dim3(B), dim3(RS_THREADS), 0, ctx->stream, (const float*)w, n, part_max);
-        hipLaunchKernelGGL(k_rs_sum, dim3(B), dim3(RS_THREADS), 0, ctx->stream, (const float*)w, n,
-                           (const float*)part_max, B, part_sum, 0);
-        hipLaunchKernelGGL(k_rs_cdf, dim3(B), dim3(RS_THREADS), 0, ctx->stream, w, n, (const float*)part_max,
-                           (const double*)part_sum, B, part_s2, cdf_rel, part_tot, part_key, out);
     }
-    hipLaunchKernelGGL(k_rs_search, dim3(B), dim3(RS_THREADS), 0, ctx->stream, n, B, (const double*)part_s2,
-                       (const unsigned long long*)part_tot, (const unsigned long long*)part_key,
-                       (const unsigned long long*)cdf_rel, ctx->cfg.resampleThresh, has_meas, seed, step, parents,
-                       out, remap ? (const phd_pose*)ctx->d_pose : nullptr, (const int*)ctx->d_src, ctx->d_tmp_pose,
-                       ctx->d_tmp_src, w, new_logw, fused ? (const float*)ctx->d_tmp_logw : nullptr, beyond);
+    RsParts P;
+    int rc = rs_parts(ctx, n, P);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_rs_max, dim3(B), dim3(RS_THREADS), 0, st, (const float*)w, n, P.part_max);
+    hipLaunchKernelGGL(k_rs_sum, dim3(B), dim3(RS_THREADS), 0, st, (const float*)w, n, (const float*)P.part_max, B,
+                       P.part_sum, 0);
+    hipLaunchKernelGGL(k_rs_cdf, dim3(B), dim3(RS_THREADS), 0, st, w, n, (const float*)P.part_max,
+                       (const double*)P.part_sum, B, P.part_s2, P.cdf_rel, P.part_tot, P.part_key, out);
+    hipLaunchKernelGGL(k_rs_search, dim3(B), dim3(RS_THREADS), 0, st, n, B, (const double*)P.part_s2,
+                       (const unsigned long long*)P.part_tot, (const unsigned long long*)P.part_key,
+                       (const unsigned long long*)P.cdf_rel, ctx->cfg.resampleThresh, ctx->M > 0 ? 1 : 0, seed, step,
+                       parents, out, remap ? (const phd_pose*)ctx->d_pose : nullptr, (const int*)ctx->d_src,
+                       ctx->d_tmp_pose, ctx->d_tmp_src, w, new_logw, (const float*)nullptr, beyond);
     HIPCHK(hipGetLastError());
     return PHD_OK;
 }
@@ -460,9 +455,18 @@ __global__ void k_iota(int* a, int n) {
 
 /* The workgroup update kernel of nt threads: part 0 the fused PHD update,
  * 1 / 2 part A / part C of the split update (CPHD: always split, with
- * k_cphd_terms between the parts; PHD: split when it pays, update_form). */
-static const void* update_kernel(int nt, int cphd, int part, int metric = 0) {
+ * k_cphd_terms between the parts; PHD: split when it pays, update_form).
+ * predict: the launch that also runs the particle's predict (the fused PHD
+ * update, CPHD's part A; up to 512 threads).  NULL: no such kernel. */
+static const void* update_kernel(int nt, int cphd, int part, int metric = 0, int predict = 0) {
     const int ti = nt == 256 ? 0 : nt == 512 ? 1 : 2;
+    if (predict) {
+        if (ti == 2) return nullptr;
+        const void* p[3][2] = {{(const void*)k_update_fused_p256, (const void*)k_update_fused_p512},
+                               {(const void*)k_update_fused_p256_h, (const void*)k_update_fused_p512_h},
+                               {(const void*)k_update_cphd_a_p256, (const void*)k_update_cphd_a_p512}};
+        return cphd ? (part == 1 ? p[2][ti] : nullptr) : (part == 0 ? p[metric == 1 ? 1 : 0][ti] : nullptr);
+    }
     if (metric == 1 && part != 1) {  // the launches that hold the merge (parts A have none)
         const void* h[3][3] = {
             {(const void*)k_update_fused_256_h, (const void*)k_update_fused_512_h, (const void*)k_update_fused_1024_h},
@@ -478,17 +482,9 @@ static const void* update_kernel(int nt, int cphd, int part, int metric = 0) {
         {{nullptr, nullptr, nullptr},
          {(const void*)k_update_cphd_a_256, (const void*)k_update_cphd_a_512, (const void*)k_update_cphd_a_1024},
          {(const void*)k_update_cphd_c_256, (const void*)k_update_cphd_c_512, (const void*)k_update_cphd_c_1024}}};
-    return k[cphd ? 1 : 0][part][nt == 256 ? 0 : nt == 512 ? 1 : 2];
+    return k[cphd ? 1 : 0][part][ti];
 }
 
-/* Threads per particle for the fused update.  The kernel is latency-bound, so
- * the step time is about (rounds of resident workgroups) x (per-workgroup
- * latency): residency from hipOccupancyMaxActiveBlocksPerMultiprocessor (LDS
- * layout, VGPRs, allocation granularity), relative latency measured at
- * config 3 (256 threads 1.25, 512 threads 1.0, 1024 threads ~0.85). */
-/* workgroups per CU of `kernel` with `lds` bytes: the LDS bound (160 KiB /
- * the layout) within the VGPR bound; hipOccupancyMaxActiveBlocksPerMultiprocessor
- * under-reports the LDS bound here (it gave 5 where 6 workgroups of 27 KB run) */
 /* LDS allocation granularity per workgroup (bytes) of the occupancy model:
  * measured on gfx950 (part C's residency timeline, stamps builds, 256 CUs): a
  * 27 120 B workgroup holds a CU to 5 (1 280 resident), a 26 864 B one to 6
@@ -498,6 +494,9 @@ static const void* update_kernel(int nt, int cphd, int part, int metric = 0) {
 #ifndef PHD_LDS_GRAN
 #define PHD_LDS_GRAN 1280
 #endif
+/* workgroups per CU of `kernel` with `lds` bytes: the LDS bound (160 KiB /
+ * the layout) within the VGPR bound; hipOccupancyMaxActiveBlocksPerMultiprocessor
+ * under-reports the LDS bound here (it gave 5 where 6 workgroups of 27 KB run) */
 static int blocks_per_cu(const void* kernel, int nt, size_t lds) {
     int vblocks = 0;  // the VGPR / wave bound alone: the runtime's answer without LDS
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&vblocks, kernel, nt, 0) != hipSuccess || vblocks <= 0)
@@ -506,6 +505,11 @@ static int blocks_per_cu(const void* kernel, int nt, size_t lds) {
     return (int)std::min<long>((160 * 1024) / (long)((lds + g - 1) / g * g), vblocks);
 }
 
+/* Threads per particle for the fused update.  The kernel is latency-bound, so
+ * the step time is about (rounds of resident workgroups) x (per-workgroup
+ * latency): residency from hipOccupancyMaxActiveBlocksPerMultiprocessor (LDS
+ * layout, VGPRs, allocation granularity), relative latency measured at
+ * config 3 (256 threads 1.25, 512 threads 1.0, 1024 threads ~0.85). */
 static int configure_update_launch(phd_ctx* c, int req) {
     const phd_capacity& cap = c->cap;
     const int cphd = c->cfg_set && c->cfg.filterType == PHD_FILTER_CPHD ? 1 : 0;
@@ -595,19 +599,8 @@ static int configure_update_launch(phd_ctx* c, int req) {
     // the fused-predict forms (CPHD: part A; PHD: the fused update) carry the
     // predict's registers: phd_step fuses the predict only when every particle's
     // workgroup of THAT launch is resident at once
-    {
-        const void* kp = nullptr;
-        size_t lp = 0;
-        if (cphd && best <= 512) {
-            kp = best == 256 ? (const void*)k_update_cphd_a_p256 : (const void*)k_update_cphd_a_p512;
-            lp = c->upd_lds_a;
-        } else if (!cphd && !best_split && best <= 512) {
-            kp = metric ? (best == 256 ? (const void*)k_update_fused_p256_h : (const void*)k_update_fused_p512_h)
-                        : (best == 256 ? (const void*)k_update_fused_p256 : (const void*)k_update_fused_p512);
-            lp = c->upd_lds;
-        }
-        c->upd_resident_p = kp ? blocks_per_cu(kp, best, lp) * ncu : 0;
-    }
+    const void* kp = update_kernel(best, cphd, best_split ? 1 : 0, metric, 1);  // (none: split PHD, 1024 threads)
+    c->upd_resident_p = kp ? blocks_per_cu(kp, best, best_split ? c->upd_lds_a : c->upd_lds) * ncu : 0;
     return PHD_OK;
 }
 
@@ -699,14 +692,9 @@ int phd_ctx_create(phd_ctx** out, int device, int n_particles, const phd_capacit
         for (int cp = 0; cp < 2; cp++)
             for (int part = cp; part < 3; part++)
                 for (int metric = 0; metric < (part == 1 ? 1 : 2); metric++)
-                    hipFuncSetAttribute(update_kernel(nt, cp, part, metric),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)k_update_fused_p256_h, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)k_update_fused_p512_h, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)k_update_cphd_a_p256, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)k_update_cphd_a_p512, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)k_update_fused_p256, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)k_update_fused_p512, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                    for (int predict = 0; predict < 2; predict++)
+                        if (const void* k = update_kernel(nt, cp, part, metric, predict))
+                            hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)k_resample, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * RS_LDS_MAX);
     hipFuncSetAttribute((const void*)k_normalize_resample, hipFuncAttributeMaxDynamicSharedMemorySize,
                         8 * RS_LDS_MAX);
@@ -746,6 +734,7 @@ int phd_set_config(phd_ctx* ctx, const phd_slam_config* cfg) {
         // Hellinger kernels their own registers
         if (set_device(ctx)) return PHD_E_HIP;
         int rc = configure_update_launch(ctx, ctx->upd_threads_req);
+        ctx->upd_cfg_error = rc ? g_last_error : std::string();  // (the launch stays sized for the old kernels)
         if (rc) return rc;
     }
     return PHD_OK;
@@ -1342,9 +1331,6 @@ static int launch_predict_dynamic(phd_ctx* ctx) {
     return PHD_OK;
 }
 
-/* The fused update of every particle, or (slots != NULL) a re-update of
- * `nslots` listed slots with the sets of the last launch (a sharded step's
- * overflow recovery: same input slabs, same output slabs, cur unchanged). */
 /* Trailing workgroups of an update launch that run at the highest wave
  * priority (UpdateArgs.prio): the ones dispatched last finish the launch, and
  * while they share SIMDs with earlier workgroups (which have slack) their
@@ -1361,8 +1347,28 @@ static int prio_tail(int grid, int resident) {
     return (int)((long)grid * UPD_PRIO_TAIL_PCT / 100);
 }
 
+/* The one-launch resample of a phd_step that its update launch carries
+ * (StepPlan): PHD_RS_FORM_LEAD in part C's lead workgroups, PHD_RS_FORM_BESIDE
+ * on the auxiliary stream beside part C. */
+struct RsBeside {
+    int form;
+    RsStepArgs a;
+};
+
+/* what an update launch tells its callers */
+struct UpdateDone {
+    bool logw_final = false;  // it recorded ev_logw (the log-weights final: phd_wait_logw)
+    bool rs_beside = false;    // the resample runs on `aux`: the context stream has to wait for ev_rs
+};
+
+/* The fused update of every particle, or (slots != NULL) a re-update of
+ * `nslots` listed slots with the sets of the last launch (a sharded step's
+ * overflow recovery: same input slabs, same output slabs, cur unchanged).
+ * rs: the step's resample to launch with part C, as its plan says. */
 static int launch_update(phd_ctx* ctx, const FusedPredict* fused = nullptr, const int* slots = nullptr,
-                         int nslots = 0) {
+                         int nslots = 0, const RsBeside* rs = nullptr, UpdateDone* done = nullptr) {
+    UpdateDone done_here;
+    if (!done) done = &done_here;
     const phd_slam_config& cfg = ctx->cfg;
     if (cfg.featureModel == PHD_FEATURE_MIXED) {
         if (slots) return fail(PHD_E_UNSUPPORTED, "feature_model 2: slot updates (sharded step) are not supported");
@@ -1381,7 +1387,6 @@ static int launch_update(phd_ctx* ctx, const FusedPredict* fused = nullptr, cons
             return fail(PHD_E_UNSUPPORTED, "CPHD update supports at most " + std::to_string(PHD_CPHD_MAX_M) +
                                                " measurements per step");
         if (cfg.maxCardinality < 0) return fail(PHD_E_ARG, "CPHD needs max_cardinality >= 0");
-        if (fused && ctx->upd_threads > 512) return fail(PHD_E_ARG, "internal: no fused predict at 1024 threads");
         const int nl = std::max(cfg.maxCardinality, ctx->cap.max_measurements) + 2;
         if (ctx->lfact_n < nl) {
             std::vector<double> lf(nl);
@@ -1394,17 +1399,19 @@ static int launch_update(phd_ctx* ctx, const FusedPredict* fused = nullptr, cons
             ctx->lfact_n = nl;
         }
         if (ensure_cn(ctx)) return PHD_E_HIP;
-        if (!ctx->upd_cphd) {
-            int rc = configure_update_launch(ctx, ctx->upd_threads_req);
-            if (rc) return rc;
-        }
     }
     if (cfg.particleWeighting != 0)
         return fail(PHD_E_UNSUPPORTED, "particle_weighting != 0 is not implemented on the device path");
-    if (ctx->upd_metric != metric) {  // the launch was sized for the other metric's kernels
-        int rc = configure_update_launch(ctx, ctx->upd_threads_req);
-        if (rc) return rc;
-    }
+    // phd_set_config sizes the launch for the filter's and the metric's kernels (registers,
+    // LDS layout); a mismatch here is its failure, reported again
+    if (ctx->upd_cphd != (cphd ? 1 : 0) || ctx->upd_metric != metric)
+        return ctx->upd_cfg_error.empty()
+                   ? fail(PHD_E_ARG, "internal: update launch not configured for this filter/metric")
+                   : fail(PHD_E_CAPACITY, ctx->upd_cfg_error);
+    // the first launch (part A of the split update, else the whole update), which runs a fused predict
+    const void* k_first = update_kernel(ctx->upd_threads, cphd, ctx->upd_split ? 1 : 0, metric, fused ? 1 : 0);
+    if (!k_first) return fail(PHD_E_ARG, "internal: no fused-predict kernel for this update form");
+    if (rs && (slots || !ctx->upd_split)) return fail(PHD_E_ARG, "internal: a step's resample without a full split update");
     const int in_set = ctx->replay ? 0 : (slots ? ctx->cur ^ 1 : ctx->cur);
     const int out_set = in_set ^ 1;
     const int grid = slots ? nslots : ctx->n;
@@ -1413,7 +1420,6 @@ static int launch_update(phd_ctx* ctx, const FusedPredict* fused = nullptr, cons
     a.n = ctx->n;
     a.slots = slots;
     a.first = 0;
-    a.prio = 0;  // set per launch (prio_tail)
     a.order = 0;
     a.cap = ctx->cap.map_capacity;
     a.M = ctx->M;
@@ -1448,14 +1454,9 @@ static int launch_update(phd_ctx* ctx, const FusedPredict* fused = nullptr, cons
     a.status = ctx->d_status;
     a.err = ctx->d_err;
     a.stamps = ctx->d_stamps;
-    a.predict = 0;
-    a.pu = phd_ackerman_control{0.f, 0.f};
     a.pc = predict_cfg(cfg, ctx->index_offset);
     a.pseed = ctx->seed;
-    a.pstep = 0;
-    a.pose_prior = nullptr;
-    a.logw_prior = nullptr;
-    if (fused) {
+    if (fused) {  // (else no predict: zeros)
         a.predict = fused->predict;
         a.pu = fused->u;
         a.pstep = fused->step;
@@ -1485,119 +1486,60 @@ static int launch_update(phd_ctx* ctx, const FusedPredict* fused = nullptr, cons
         PHD_TIMING_EVENTS && !ctx->ev_a.empty() && !slots && ctx->timing_tick++ % ctx->timing_stride == 0;
     const int ei = ctx->ev_next;
     if (timed) HIPCHK(hipEventRecord(ctx->ev_a[ei], ctx->stream));
-    // the launches of one chunk of particles [a.first, a.first + grid) on stream st
-    // PHD_RS_OVERLAP: once the log-weights are final (after the CPHD terms
-    // launch, or after the split PHD update's part A) the step's resample runs
-    // on the auxiliary stream beside part C; part C reads neither the
-    // log-weights nor the arrays the resample writes
-    // PHD_RS_LEAD: instead, part C's lead workgroup runs it (rs_step_block): the
-    // launch gets RS_LEAD_WGS workgroups in front (the others return at once,
-    // so every particle keeps its XCD) and no event crosses streams.  Returns
-    // the lead workgroups of the part C launch.  (The diagnostic stamps build
-    // indexes its records by workgroup: it keeps the second stream.)
-    auto rs_lead = [&](UpdateArgs& x) -> int {
-        if (!PHD_RS_LEAD || !ctx->rs_ov.armed || slots || x.stamps) return 0;
-        // (part C's LDS must hold rs_step_block's tables: with small capacities
-        // it does not, and the resample takes the second stream instead)
-        if ((size_t)ctx->upd_lds < rs_step_lds(ctx->upd_threads)) return 0;
-        x.rs_lead = RS_LEAD_WGS;
-        x.rs = ctx->rs_ov.a;
-        ctx->rs_ov.launched = true;
-        ctx->rs_ov.lead = true;
-        return RS_LEAD_WGS;
-    };
-    auto rs_beside = [&](hipStream_t st) {
-        if (!ctx->rs_ov.armed || slots || ctx->rs_ov.launched) return;
-        hipEventRecord(ctx->ev_terms, st);
-        hipStreamWaitEvent(ctx->aux, ctx->ev_terms, 0);
-        hipLaunchKernelGGL(k_rs_step, dim3(ctx->rs_ov.B), dim3(RS_THREADS), 0, ctx->aux, ctx->rs_ov.a);
-        hipEventRecord(ctx->ev_rs, ctx->aux);
-        ctx->rs_ov.launched = true;
-    };
-    auto chain = [&](UpdateArgs a, int grid, hipStream_t st) {
-        if (grid <= 0) return;
-        a.prio = prio_tail(grid, ctx->upd_resident);
-        if (cphd) {
-            // part A -> CPHD terms (one wave per particle) -> part C (the diagnostic
-            // phase stamps record part C)
-            UpdateArgs aa = a;
-            aa.stamps = nullptr;
+    hipStream_t st = ctx->stream;
+    const dim3 block(ctx->upd_threads);
+    a.prio = prio_tail(grid, ctx->upd_resident);
+    if (ctx->upd_split) {
+        // part A -> (CPHD: the terms, one wave per particle) -> part C through the
+        // handoff (the diagnostic phase stamps record part C)
+        UpdateArgs aa = a;
+        aa.stamps = nullptr;
 #ifdef PHD_STAMP_PART_A
-            aa.stamps = a.stamps;  // diagnostic stamps build: record part A instead
-            a.stamps = nullptr;
+        aa.stamps = a.stamps;  // diagnostic stamps build: record part A instead
+        a.stamps = nullptr;
 #endif
-            // part A runs the particle's predict when fused (the CPHD update is three
-            // launches: the predict's registers cost part A nothing that matters)
-            const void* ka = fused ? (ctx->upd_threads == 256 ? (const void*)k_update_cphd_a_p256
-                                                                : (const void*)k_update_cphd_a_p512)
-                                   : update_kernel(ctx->upd_threads, 1, 1);
-            aa.prio = prio_tail(grid, ctx->upd_resident_a);
-            hipLaunchKernelGGL((void (*)(UpdateArgs))ka, dim3(grid), dim3(ctx->upd_threads), ctx->upd_lds_a, st,
-                               aa);
-            // the fused predict is done: parts B and C read the predicted poses
-            a.predict = 0;
-            a.pose_prior = nullptr;
-            a.logw_prior = nullptr;
-            // the terms and part C read part A's handoff and prior slab: last-written first
-            a.order = 1;
+        // CPHD's part A runs the particle's predict when fused (the CPHD update is
+        // three launches: the predict's registers cost part A nothing that matters);
+        // the split PHD update's never (enqueue_predict_update: its own launch)
+        aa.prio = prio_tail(grid, ctx->upd_resident_a);
+        hipLaunchKernelGGL((void (*)(UpdateArgs))k_first, dim3(grid), block, ctx->upd_lds_a, st, aa);
+        // the fused predict is done: the later launches read the predicted poses
+        a.predict = 0;
+        a.pose_prior = nullptr;
+        a.logw_prior = nullptr;
+        // the terms and part C read part A's handoff and prior slab: last-written
+        // first, XCD-preserving (upd_particle)
+        a.order = 1;
+        if (cphd)
             hipLaunchKernelGGL(k_cphd_terms, dim3(grid), dim3(64), cphd_terms_lds(ctx->cap.max_measurements), st,
                                a);
-            if (ctx->ev_logw) {  // the log-weights are final (phd_wait_logw)
-                hipEventRecord(ctx->ev_logw, st);
-                ctx->logw_marked = true;
-            }
-            const int lead = rs_lead(a);
-            rs_beside(st);
-            hipLaunchKernelGGL((void (*)(UpdateArgs))update_kernel(ctx->upd_threads, 1, 2, metric), dim3(grid + lead),
-                               dim3(ctx->upd_threads), ctx->upd_lds, st, a);
-            ctx->cn_valid = true;
-        } else if (ctx->upd_split) {
-            // split PHD update: part A -> part C through the handoff (the predict ran
-            // as its own launch: enqueue_predict_update does not fuse it here)
-            UpdateArgs aa = a;
-            aa.stamps = nullptr;
-#ifdef PHD_STAMP_PART_A
-            aa.stamps = a.stamps;
-            a.stamps = nullptr;
-#endif
-            aa.prio = prio_tail(grid, ctx->upd_resident_a);
-            hipLaunchKernelGGL((void (*)(UpdateArgs))update_kernel(ctx->upd_threads, 0, 1), dim3(grid),
-                               dim3(ctx->upd_threads), ctx->upd_lds_a, st, aa);
-            if (ctx->ev_logw) {  // part A wrote the log-weights (phd_wait_logw)
-                hipEventRecord(ctx->ev_logw, st);
-                ctx->logw_marked = true;
-            }
-            const int lead = rs_lead(a);
-            rs_beside(st);
-            a.predict = 0;
-            a.pose_prior = nullptr;
-            a.logw_prior = nullptr;
-            a.order = 1;  // last-written first, XCD-preserving (upd_particle)
-            hipLaunchKernelGGL((void (*)(UpdateArgs))update_kernel(ctx->upd_threads, 0, 2, metric), dim3(grid + lead),
-                               dim3(ctx->upd_threads), ctx->upd_lds, st, a);
-        } else if (metric == 1) {
-            const void* kh = fused && ctx->upd_threads == 256   ? (const void*)k_update_fused_p256_h
-                             : fused && ctx->upd_threads == 512 ? (const void*)k_update_fused_p512_h
-                                                                : update_kernel(ctx->upd_threads, 0, 0, 1);
-            hipLaunchKernelGGL((void (*)(UpdateArgs))kh, dim3(grid), dim3(ctx->upd_threads), ctx->upd_lds, st, a);
-        } else if (fused && ctx->upd_threads == 256) {
-            hipLaunchKernelGGL(k_update_fused_p256, dim3(grid), dim3(256), ctx->upd_lds, st, a);
-        } else if (fused && ctx->upd_threads == 512) {
-            hipLaunchKernelGGL(k_update_fused_p512, dim3(grid), dim3(512), ctx->upd_lds, st, a);
-        } else {
-            switch (ctx->upd_threads) {
-                case 256: hipLaunchKernelGGL(k_update_fused_256, dim3(grid), dim3(256), ctx->upd_lds, st, a); break;
-                case 512: hipLaunchKernelGGL(k_update_fused_512, dim3(grid), dim3(512), ctx->upd_lds, st, a); break;
-                default: hipLaunchKernelGGL(k_update_fused_1024, dim3(grid), dim3(1024), ctx->upd_lds, st, a); break;
-            }
+        if (ctx->ev_logw) {  // the log-weights are final (phd_wait_logw)
+            hipEventRecord(ctx->ev_logw, st);
+            done->logw_final = true;
         }
-    };
-    ctx->logw_marked = false;
-    chain(a, grid, ctx->stream);
+        // the step's resample, now that the log-weights are final: part C reads
+        // neither them nor the arrays the resample writes
+        int lead = 0;
+        if (rs && rs->form == PHD_RS_FORM_LEAD) {  // in part C's lead workgroups: ordered by the stream itself
+            a.rs_lead = lead = RS_LEAD_WGS;
+            a.rs = rs->a;
+        } else if (rs) {  // PHD_RS_FORM_BESIDE: on the auxiliary stream
+            hipEventRecord(ctx->ev_terms, st);
+            hipStreamWaitEvent(ctx->aux, ctx->ev_terms, 0);
+            hipLaunchKernelGGL(k_rs_step, dim3(rs->a.B), dim3(RS_THREADS), 0, ctx->aux, rs->a);
+            hipEventRecord(ctx->ev_rs, ctx->aux);
+            done->rs_beside = true;
+        }
+        hipLaunchKernelGGL((void (*)(UpdateArgs))update_kernel(ctx->upd_threads, cphd, 2, metric), dim3(grid + lead),
+                           block, ctx->upd_lds, st, a);
+        if (cphd) ctx->cn_valid = true;
+    } else {
+        hipLaunchKernelGGL((void (*)(UpdateArgs))k_first, dim3(grid), block, ctx->upd_lds, st, a);
+    }
     HIPCHK(hipGetLastError());
-    if (ctx->ev_logw && !ctx->logw_marked) {  // (the fused update: its log-weights at its end)
-        HIPCHK(hipEventRecord(ctx->ev_logw, ctx->stream));
-        ctx->logw_marked = true;
+    if (ctx->ev_logw && !done->logw_final) {  // (the fused update: its log-weights at its end)
+        HIPCHK(hipEventRecord(ctx->ev_logw, st));
+        done->logw_final = true;
     }
     if (!slots) ctx->src_fresh = true;  // part C reset every slab reference to the identity
     if (timed) {
@@ -1870,32 +1812,26 @@ int phd_apply_resample(phd_ctx* ctx, const int* dev_idx, float new_log_weight) {
 }
 
 /* predict (fused into the update when it pays) + update: the part of a step
- * before the cross-particle normalisation. */
+ * before the cross-particle normalisation.  rs / done: launch_update's. */
 static int enqueue_predict_update(phd_ctx* ctx, const phd_ackerman_control* u, int do_predict, uint64_t step,
-                                  const int* slots = nullptr, int nslots = 0) {
+                                  const int* slots = nullptr, int nslots = 0, const RsBeside* rs = nullptr,
+                                  UpdateDone* done = nullptr) {
     const phd_slam_config& cfg = ctx->cfg;
     int rc;
     const int count = slots ? nslots : ctx->n;
-    // the step's births are placed by the update's classify from the predicted
-    // pose (also when the predict is fused into the update)
-    const bool births = step_births_on(ctx) && cfg.featureModel == PHD_FEATURE_STATIC;
-    if (do_predict && ctx->M > 0 && cfg.nPredictParticles == 1 && cfg.featureModel == PHD_FEATURE_STATIC &&
+    FusedPredict fp;
+    // predict fused into the update launch when every particle's workgroup is
+    // resident at once (saves a launch); with several rounds of workgroups the
+    // serial per-particle predict would sit on each round's critical path
+    const bool fuse =
+        do_predict && ctx->M > 0 && cfg.nPredictParticles == 1 && cfg.featureModel == PHD_FEATURE_STATIC &&
         (ctx->n <= ctx->upd_resident_p || (PHD_FUSE_PREDICT_ALL && cfg.filterType == PHD_FILTER_CPHD)) &&
-        ctx->upd_threads <= 512 && (cfg.filterType == PHD_FILTER_CPHD || !ctx->upd_split)) {
-        // predict fused into the update launch when every particle's workgroup is
-        // resident at once (saves a launch); with several rounds of workgroups the
-        // serial per-particle predict would sit on each round's critical path
-        FusedPredict fp;
+        ctx->upd_threads <= 512 && (cfg.filterType == PHD_FILTER_CPHD || !ctx->upd_split);
+    if (fuse) {
         fp.predict = cfg.motionType == PHD_MOTION_ACKERMAN ? 1 : 2;
         if (fp.predict == 1 && !u) return fail(PHD_E_ARG, "Ackerman predict needs a control");
         fp.u = u ? *u : phd_ackerman_control{0.f, 0.f};
         fp.step = step;
-        if (births) {
-            rc = launch_step_births(ctx, slots, slots ? count : ctx->n);
-            if (rc) return rc;
-        }
-        rc = launch_update(ctx, &fp, slots, nslots);
-        if (rc) return rc;
     } else if (do_predict) {
         rc = check_predict(ctx);
         if (rc) return rc;
@@ -1910,24 +1846,14 @@ static int enqueue_predict_update(phd_ctx* ctx, const phd_ackerman_control* u, i
                                 slots ? count : ctx->n);
             if (rc) return rc;
         }
-        if (births) {
-            rc = launch_step_births(ctx, slots, slots ? count : ctx->n);
-            if (rc) return rc;
-        }
-        if (ctx->M > 0) {
-            rc = launch_update(ctx, nullptr, slots, nslots);
-            if (rc) return rc;
-        }
-    } else {
-        if (births) {
-            rc = launch_step_births(ctx, slots, slots ? count : ctx->n);
-            if (rc) return rc;
-        }
-        if (ctx->M > 0) {
-            rc = launch_update(ctx, nullptr, slots, nslots);
-            if (rc) return rc;
-        }
     }
+    // the step's births are placed by the update's classify from the predicted
+    // pose (also when the predict is fused into the update)
+    if (step_births_on(ctx) && cfg.featureModel == PHD_FEATURE_STATIC) {
+        rc = launch_step_births(ctx, slots, slots ? count : ctx->n);
+        if (rc) return rc;
+    }
+    if (ctx->M > 0) return launch_update(ctx, fuse ? &fp : nullptr, slots, nslots, rs, done);
     return PHD_OK;
 }
 
@@ -1941,8 +1867,8 @@ int phd_predict_update(phd_ctx* ctx, const phd_ackerman_control* u, int do_predi
     const bool mirror = dev_logw_out && ctx->M > 0 && ctx->cfg.featureModel == PHD_FEATURE_STATIC &&
                         ctx->cfg.nPredictParticles <= 1 && ctx->n == ctx->n_base;
     ctx->logw_mirror = mirror ? dev_logw_out : nullptr;
-    ctx->logw_marked = false;
-    int rc = enqueue_predict_update(ctx, u, do_predict, step);
+    UpdateDone done;
+    int rc = enqueue_predict_update(ctx, u, do_predict, step, nullptr, 0, nullptr, &done);
     ctx->logw_mirror = nullptr;
     if (rc) return rc;
     if (dev_logw_out && !mirror)
@@ -1951,7 +1877,7 @@ int phd_predict_update(phd_ctx* ctx, const phd_ackerman_control* u, int do_predi
     // phd_wait_logw promises the mirror complete: when no update marked the
     // log-weights final this call (an empty scan: no update at all) or the
     // mirror is a copy, mark them after it
-    if (ctx->ev_logw && (!ctx->logw_marked || (dev_logw_out && !mirror)))
+    if (ctx->ev_logw && (!done.logw_final || (dev_logw_out && !mirror)))
         HIPCHK(hipEventRecord(ctx->ev_logw, ctx->stream));
     return PHD_OK;
 }
@@ -2207,132 +2133,123 @@ int phd_trace_shard_append(phd_ctx* ctx, const float* dev_w_all, const void* dev
     return PHD_OK;
 }
 
+/* the end of a phd_step: the update's error check, then nEff and the decision
+ * to the host when asked for */
+static int step_read_back(phd_ctx* ctx, float* neff_out, int* resampled) {
+    if (ctx->M > 0 && ctx->check_each_update) {
+        int rc = check_err(ctx);
+        if (rc) return rc;
+    }
+    if (!neff_out && !resampled) return PHD_OK;
+    float out[3];
+    HIPCHK(hipMemcpyAsync(out, ctx->d_out, 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    int f;
+    memcpy(&f, &out[2], sizeof(int));
+    if (neff_out) *neff_out = out[1];
+    if (resampled) *resampled = f;
+    return PHD_OK;
+}
+
+static_assert(kRsChunk == RS_THREADS, "phd_step_plan.h: the chunk of the resample kernels");
+
 int phd_step(phd_ctx* ctx, const phd_ackerman_control* u, int do_predict, uint64_t step, float* neff_out,
              int* resampled) {
     if (!ctx) return fail(PHD_E_ARG, "null ctx");
     if (!ctx->cfg_set) return fail(PHD_E_ARG, "phd_set_config not called");
     if (set_device(ctx)) return PHD_E_HIP;
     const phd_slam_config& cfg = ctx->cfg;
-    // chunked normalise up to 16 chunks: each block takes the max of all
-    // entries itself instead of a k_rs_max launch (same max, same bits)
-    const bool fuse_max = ctx->n <= 16 * RS_THREADS;
-    // normalise + nEff + device-side resample decision + resample (main.cpp:1281-1297)
-    const float neglogn = (float)(-std::log((double)ctx->n));
-    // PHD_RS_OVERLAP: the one-launch resample beside part C of a CPHD step (its
-    // log-weights are final after the terms launch) or of a split PHD step
-    // (final after part A); armed only records its arguments, and a chain that
-    // does not launch it (the fused PHD update) leaves it to the main stream
-    // below.  Its workgroups wait out part C on their CUs, so only while part C
-    // is a few rounds of resident workgroups (config 4's per-GPU shard, 2.7
-    // rounds: 3 409 -> 3 504 steps/s; config 5's, 16 rounds: 674 -> 645)
-    // a traced step (phd_trace_enable) reads the poses and the log-weights the
-    // resample rewrites: its resample runs after the update and the trace
     const bool traced = ctx->tr.cap > 0;
     if (traced) {
         int rc0 = trace_supported(ctx, TRACE_STEP);
         if (rc0) return rc0;
     }
-    const bool overlap = !traced &&
-                         (cfg.filterType == PHD_FILTER_CPHD ? (PHD_RS_OVERLAP & 1) : ctx->upd_split && (PHD_RS_OVERLAP & 2)) &&
-                         ctx->n <= 4 * ctx->upd_resident && cfg.nPredictParticles <= 1 &&
-                         ctx->n == ctx->n_base && ctx->n > 2 * RS_THREADS && fuse_max && ctx->M > 0 &&
-                         cfg.featureModel == PHD_FEATURE_STATIC;
-    if (overlap) {
-        if (!ctx->aux) {
+    // the step's resample form, decided before anything is enqueued
+    StepFacts facts{};
+    facts.n = ctx->n;
+    facts.n_base = ctx->n_base;
+    facts.n_predict_particles = cfg.nPredictParticles;
+    facts.M = ctx->M;
+    facts.filter_type = cfg.filterType;
+    facts.feature_model = cfg.featureModel;
+    facts.upd_split = ctx->upd_split;
+    facts.upd_resident = ctx->upd_resident;
+    facts.upd_lds = ctx->upd_lds;
+    facts.rs_step_lds = rs_step_lds(ctx->upd_threads);
+    facts.traced = traced;
+    facts.stamps = ctx->d_stamps != nullptr;
+#ifdef PHD_STAMP_PART_A
+    facts.stamps = false;  // (that diagnostic build records part A: part C carries no stamps)
+#endif
+    facts.overlap_bits = PHD_RS_OVERLAP;
+    facts.lead_on = PHD_RS_LEAD;
+    const StepPlan plan = plan_step(facts);
+    // normalise + nEff + device-side resample decision + resample (main.cpp:1281-1297)
+    const float neglogn = (float)(-std::log((double)ctx->n));
+    RsBeside rs{plan.form, {}};
+    const bool with_update = plan.form == PHD_RS_FORM_LEAD || plan.form == PHD_RS_FORM_BESIDE;
+    if (with_update) {  // the update launches it with part C
+        if (!ctx->aux) {  // (the auxiliary stream and its events: used by PHD_RS_FORM_BESIDE)
             int lo = 0, hi = 0;
             HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
             HIPCHK(hipStreamCreateWithPriority(&ctx->aux, hipStreamNonBlocking, hi));
             HIPCHK(hipEventCreateWithFlags(&ctx->ev_terms, kEvOrder));
             HIPCHK(hipEventCreateWithFlags(&ctx->ev_rs, kEvOrder));
         }
-        ctx->rs_ov.armed = true;
-        ctx->rs_ov.launched = false;
-        ctx->rs_ov.lead = false;
-        int rc0 = launch_rs_chunks(ctx, ctx->d_logw, ctx->n, ctx->d_out, ctx->seed, step, ctx->d_idx, true, neglogn,
-                                   fuse_max);  // (armed: only records the launch's arguments)
-        if (rc0) {
-            ctx->rs_ov.armed = false;
-            return rc0;
-        }
+        int rc0 = rs_step_args(ctx, ctx->d_logw, ctx->n, ctx->d_out, ctx->seed, step, ctx->d_idx, neglogn, rs.a);
+        if (rc0) return rc0;
+        rs.a.src = nullptr;  // the update resets the slab references to the identity
     }
-    int rc = enqueue_predict_update(ctx, u, do_predict, step);
-    // (in the lead workgroup: ordered by the stream itself, no event to wait on)
-    const bool ov_launched = ctx->rs_ov.launched && !ctx->rs_ov.lead;
-    const bool ov_done = ctx->rs_ov.launched;
-    ctx->rs_ov.armed = false;
-    ctx->rs_ov.launched = false;
-    ctx->rs_ov.lead = false;
+    UpdateDone done;
+    int rc = enqueue_predict_update(ctx, u, do_predict, step, nullptr, 0, with_update ? &rs : nullptr, &done);
     if (rc) {
         // the resample may already run on the auxiliary stream (it writes the
         // log-weights, the parents and the spare pose / slab arrays): order
         // everything the caller enqueues next after it
-        if (ov_launched) hipStreamWaitEvent(ctx->stream, ctx->ev_rs, 0);
+        if (done.rs_beside) hipStreamWaitEvent(ctx->stream, ctx->ev_rs, 0);
         return rc;
     }
     if (traced) {
         rc = trace_append(ctx, step);
         if (rc) return rc;
     }
-    if (cfg.nPredictParticles > 1 || ctx->n != ctx->n_base) {
-        // live count above n_particles: the resample draws n_particles children
-        // and the next step's launches depend on the decision, so it is read
-        // back here (one host synchronisation per step in this mode)
-        hipLaunchKernelGGL(k_normalize, dim3(1), dim3(1024), 0, ctx->stream, ctx->d_logw, ctx->n,
-                           (const float*)nullptr, ctx->d_out, cfg.resampleThresh, rs_mode(ctx));
-        HIPCHK(hipGetLastError());
-        rc = launch_resample(ctx, (const int*)(ctx->d_out + 2), nullptr, step);
-        if (rc) return rc;
-        if (ctx->M > 0 && ctx->check_each_update) {
-            rc = check_err(ctx);
+    ctx->rs_form = plan.form;
+    switch (plan.form) {
+        case PHD_RS_FORM_SEPARATE: {
+            hipLaunchKernelGGL(k_normalize, dim3(1), dim3(1024), 0, ctx->stream, ctx->d_logw, ctx->n,
+                               (const float*)nullptr, ctx->d_out, cfg.resampleThresh, rs_mode(ctx));
+            HIPCHK(hipGetLastError());
+            rc = launch_resample(ctx, (const int*)(ctx->d_out + 2), nullptr, step);
             if (rc) return rc;
-        }
-        float out[3];
-        HIPCHK(hipMemcpyAsync(out, ctx->d_out, 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        int f;
-        memcpy(&f, &out[2], sizeof(int));
-        if (f) ctx->n = ctx->n_base;
-        ctx->rs_form = PHD_RS_FORM_SEPARATE;
-        if (neff_out) *neff_out = out[1];
-        if (resampled) *resampled = f;
-        return PHD_OK;
-    }
-    if (ctx->n <= 2 * RS_THREADS) {  // one launch: a single block is fastest here
-        ctx->rs_form = PHD_RS_FORM_BLOCK;
-        hipLaunchKernelGGL(k_normalize_resample, dim3(1), dim3(1024), rs_lds(ctx->n), ctx->stream, ctx->d_logw,
-                           ctx->n, ctx->d_out, cfg.resampleThresh, ctx->M > 0 ? 1 : 0, ctx->seed, step, ctx->d_cdf,
-                           ctx->d_idx, ctx->d_pose, ctx->d_src, ctx->d_tmp_pose, ctx->d_tmp_src, neglogn);
-        HIPCHK(hipGetLastError());
-    } else {  // chunked over n/1024 workgroups; the search writes the remap into the spare arrays
-        if (ov_done) {
-            ctx->rs_form = ov_launched ? PHD_RS_FORM_BESIDE : PHD_RS_FORM_LEAD;
-            if (ov_launched) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_rs, 0));  // (ran beside part C)
-        } else {
-            ctx->rs_form = fuse_max ? PHD_RS_FORM_STEP : PHD_RS_FORM_CHUNKS;  // (launch_rs_chunks: fused up to 16 chunks)
-            rc = launch_rs_chunks(ctx, ctx->d_logw, ctx->n, ctx->d_out, ctx->seed, step, ctx->d_idx, true, neglogn,
-                                  fuse_max);
+            int f = 0;
+            rc = step_read_back(ctx, neff_out, &f);  // (the next step's launches depend on the decision)
             if (rc) return rc;
+            if (f) ctx->n = ctx->n_base;
+            if (resampled) *resampled = f;
+            return PHD_OK;
         }
-        std::swap(ctx->d_pose, ctx->d_tmp_pose);  // identity copy when no resample was decided
-        std::swap(ctx->d_src, ctx->d_tmp_src);
-        ctx->src_fresh = false;  // (a remap, when the device decided to resample)
+        case PHD_RS_FORM_BLOCK:
+            hipLaunchKernelGGL(k_normalize_resample, dim3(1), dim3(1024), rs_lds(ctx->n), ctx->stream, ctx->d_logw,
+                               ctx->n, ctx->d_out, cfg.resampleThresh, ctx->M > 0 ? 1 : 0, ctx->seed, step,
+                               ctx->d_cdf, ctx->d_idx, ctx->d_pose, ctx->d_src, ctx->d_tmp_pose, ctx->d_tmp_src,
+                               neglogn);
+            HIPCHK(hipGetLastError());
+            return step_read_back(ctx, neff_out, resampled);
+        case PHD_RS_FORM_BESIDE:  // (ran beside part C)
+            HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_rs, 0));
+            break;
+        case PHD_RS_FORM_LEAD:  // (in the lead workgroup: ordered by the stream itself, no event to wait on)
+            break;
+        default:  // PHD_RS_FORM_STEP / _CHUNKS: chunked over n/1024 workgroups of the context stream
+            rc = launch_rs_chunks(ctx, ctx->stream, ctx->d_logw, ctx->n, ctx->d_out, ctx->seed, step, ctx->d_idx, true,
+                                  neglogn, plan.fuse_max);
+            if (rc) return rc;
     }
-    if (ctx->M > 0 && ctx->check_each_update) {
-        rc = check_err(ctx);
-        if (rc) return rc;
-    }
-    if (neff_out || resampled) {
-        float out[3];
-        HIPCHK(hipMemcpyAsync(out, ctx->d_out, 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (neff_out) *neff_out = out[1];
-        if (resampled) {
-            int f;
-            memcpy(&f, &out[2], sizeof(int));
-            *resampled = f;
-        }
-    }
-    return PHD_OK;
+    // the chunked forms' search wrote the remap into the spare arrays
+    std::swap(ctx->d_pose, ctx->d_tmp_pose);  // identity copy when no resample was decided
+    std::swap(ctx->d_src, ctx->d_tmp_src);
+    ctx->src_fresh = false;  // (a remap, when the device decided to resample)
+    return step_read_back(ctx, neff_out, resampled);
 }
 
 __global__ void k_fill(float* a, int n, float v) {
@@ -2431,9 +2348,9 @@ static int ensure_mig(phd_ctx* ctx, int world) {
 /* The sharded plan (global normalise / nEff / decision / parents, then this
  * rank's migration plan and remap): one k_shard_plan launch when its
  * ceil(N/1024) workgroups can all be resident (every config here: <= 256), else
- * the k_rs_* chain + k_shard_tail. */
-static int launch_shard_plan(phd_ctx* ctx, float* dev_w_all, int world, int rank, uint64_t seed, uint64_t step,
-                             int* dev_parents, int* dev_keep_src, int* dev_send_src, int* dev_recv_rec,
+ * the k_rs_* chain + k_shard_tail; on stream st. */
+static int launch_shard_plan(phd_ctx* ctx, hipStream_t st, float* dev_w_all, int world, int rank, uint64_t seed,
+                             uint64_t step, int* dev_parents, int* dev_keep_src, int* dev_send_src, int* dev_recv_rec,
                              float new_log_weight, int block_records, bool chain = false, bool with_src = true) {
     const int n_total = world * ctx->n;
     const int B = (n_total + RS_THREADS - 1) / RS_THREADS;
@@ -2477,14 +2394,14 @@ static int launch_shard_plan(phd_ctx* ctx, float* dev_w_all, int world, int rank
         a.new_pose = ctx->d_tmp_pose;
         a.new_src = ctx->d_tmp_src;
         a.logw_local = ctx->d_logw;
-        hipLaunchKernelGGL(k_shard_plan, dim3(B), dim3(RS_THREADS), 0, ctx->stream, a);
+        hipLaunchKernelGGL(k_shard_plan, dim3(B), dim3(RS_THREADS), 0, st, a);
         HIPCHK(hipGetLastError());
         return PHD_OK;
     }
-    int rc = launch_rs_chunks(ctx, dev_w_all, n_total, out, seed, step, dev_parents, false, 0.f, false,
+    int rc = launch_rs_chunks(ctx, st, dev_w_all, n_total, out, seed, step, dev_parents, false, 0.f, false,
                               ctx->d_plan_sync + PLAN_BEYOND);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_shard_tail, dim3(1), dim3(RS_THREADS), 0, ctx->stream, (const float*)dev_w_all, ctx->n,
+    hipLaunchKernelGGL(k_shard_tail, dim3(1), dim3(RS_THREADS), 0, st, (const float*)dev_w_all, ctx->n,
                        world, rank, (const float*)out, (const int*)dev_parents, ctx->d_plan_sync, ctx->d_mig,
                        ctx->h_mig_dev, dev_keep_src, dev_send_src, dev_recv_rec, (const phd_pose*)ctx->d_pose, src,
                        ctx->d_tmp_pose, ctx->d_tmp_src, ctx->d_logw, new_log_weight, block_records, ctx->d_pend,
@@ -2509,8 +2426,8 @@ int phd_shard_resample(phd_ctx* ctx, float* dev_w_all, int world, int rank, uint
     const int n_total = world * ctx->n;
     if (ensure_mig(ctx, world)) return PHD_E_HIP;
     // the global part and this rank's plan (k_shard_plan, or the k_rs_* chain + k_shard_tail)
-    int rc = launch_shard_plan(ctx, dev_w_all, world, rank, seed, step, dev_parents, dev_keep_src, dev_send_src,
-                               dev_recv_rec, new_log_weight, ctx->n);
+    int rc = launch_shard_plan(ctx, ctx->stream, dev_w_all, world, rank, seed, step, dev_parents, dev_keep_src,
+                               dev_send_src, dev_recv_rec, new_log_weight, ctx->n);
     if (rc) return rc;
     if (send_capacity > 0) {
         if (ensure_cn(ctx)) return PHD_E_HIP;
@@ -2579,11 +2496,8 @@ int phd_shard_resample_async(phd_ctx* ctx, float* dev_w_all, int world, int rank
             HIPCHK(hipEventRecord(ctx->ev_plan, ctx->stream));
             HIPCHK(hipStreamWaitEvent(ctx->plan_stream, ctx->ev_plan, 0));
         }
-        hipStream_t main = ctx->stream;
-        ctx->stream = ctx->plan_stream;
-        rc = launch_shard_plan(ctx, dev_w_all, world, rank, seed, step, dev_parents, dev_keep_src, dev_send_src,
-                               dev_recv_rec, new_log_weight, block_records, true, !ctx->src_fresh);
-        ctx->stream = main;
+        rc = launch_shard_plan(ctx, ctx->plan_stream, dev_w_all, world, rank, seed, step, dev_parents, dev_keep_src,
+                               dev_send_src, dev_recv_rec, new_log_weight, block_records, true, !ctx->src_fresh);
         if (rc) return rc;
         if (PHD_PLAN_WAIT_KERNEL) {
             // the pack / the next step wait for the plan inside the context
@@ -2598,8 +2512,8 @@ int phd_shard_resample_async(phd_ctx* ctx, float* dev_w_all, int world, int rank
             HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_plan, 0));
         }
     } else {
-        rc = launch_shard_plan(ctx, dev_w_all, world, rank, seed, step, dev_parents, dev_keep_src, dev_send_src,
-                               dev_recv_rec, new_log_weight, block_records);
+        rc = launch_shard_plan(ctx, ctx->stream, dev_w_all, world, rank, seed, step, dev_parents, dev_keep_src,
+                               dev_send_src, dev_recv_rec, new_log_weight, block_records);
         if (rc) return rc;
     }
     if (world > 1) {  // records from the pre-resample store (the pointers are swapped below)
