@@ -583,9 +583,16 @@ struct EapScratch {
     void* buf = nullptr;
     size_t bytes = 0;
     int* pinned = nullptr;  // read-back slots of the decision rounds
+    std::vector<int> off;   // host offsets of the last collect / pack
+    int* pin_off = nullptr; // pinned copy of off for the pack's upload (the pack does not wait for it)
+    int pin_off_n = 0;
+    int* heads = nullptr;   // sharded form: world + 1 offsets | EAP_HS_WORDS summary words
+    int heads_world = 0;
     ~EapScratch() {
         if (buf) hipFree(buf);
         if (pinned) hipHostFree(pinned);
+        if (pin_off) hipHostFree(pin_off);
+        if (heads) hipFree(heads);
     }
 };
 
@@ -668,31 +675,27 @@ static int bits_for(unsigned int v) {  // radix bits covering 0..v
     return b;
 }
 
-/* Expected map of the current store into host `out` (out_cap entries).
- * Returns the component count (also when it exceeds out_cap: nothing is then
- * copied), or -1 on a HIP error (err).  *n_groups = independent groups. */
-long eap_run(EapScratch** sp, hipStream_t st, const int* d_src, const float* d_map, const int* d_size,
-             const float* d_map_x, const int* d_size_x, const float* d_logw, int n, int cap, float T,
-             phd_gaussian2d* out, long out_cap, int* n_groups, std::string& err) {
-    if (!*sp) *sp = new EapScratch();
-    EapScratch& S = **sp;
-    auto ensure = [&](size_t need) -> int {
-        if (S.bytes >= need) return 0;
-        if (S.buf) hipFree(S.buf);
-        S.buf = nullptr;
-        S.bytes = 0;
-        if (hipMalloc(&S.buf, need) != hipSuccess) return -1;
-        S.bytes = need;
-        return 0;
-    };
-    if (n_groups) *n_groups = 0;
-    // component counts -> offsets (one read-back of n ints)
-    if (ensure((size_t)(n + 1) * sizeof(int))) {
+static int eap_ensure(EapScratch& S, size_t need) {
+    if (S.bytes >= need) return 0;
+    if (S.buf) hipFree(S.buf);
+    S.buf = nullptr;
+    S.bytes = 0;
+    if (hipMalloc(&S.buf, need) != hipSuccess) return -1;
+    S.bytes = need;
+    return 0;
+}
+
+/* Component counts of the store -> S.off (n + 1 host offsets), one read-back
+ * of n ints.  Returns the component count, or -1 (err). */
+static long eap_offsets(EapScratch& S, hipStream_t st, const int* d_src, const int* d_size, const int* d_size_x, int n,
+                        std::string& err) {
+    if (eap_ensure(S, (size_t)(n + 1) * sizeof(int))) {
         err = "expected map: out of device memory";
         return -1;
     }
     hipLaunchKernelGGL(k_eap_sizes, dim3((n + 255) / 256), dim3(256), 0, st, d_src, d_size, d_size_x, n, (int*)S.buf);
-    std::vector<int> off(n + 1, 0);
+    std::vector<int>& off = S.off;
+    off.assign(n + 1, 0);
     EAPCHK(hipMemcpyAsync(off.data() + 1, S.buf, n * sizeof(int), hipMemcpyDeviceToHost, st));
     EAPCHK(hipStreamSynchronize(st));
     long Kl = 0;
@@ -700,12 +703,15 @@ long eap_run(EapScratch** sp, hipStream_t st, const int* d_src, const float* d_m
         Kl += off[p + 1];
         off[p + 1] = (int)Kl;
     }
-    if (Kl == 0) return 0;
     if (Kl >= (1L << 31) - 1) {
         err = "expected map: more than 2^31 components";
         return -1;
     }
-    const long K = Kl;
+    return Kl;
+}
+
+/* The reduce stage's scratch for K components (and n + 1 offsets), carved. */
+static int eap_scratch(EapScratch& S, hipStream_t st, long K, int n, EapBufs* B, size_t* tmp_bytes, std::string& err) {
     const int Ki = (int)K;
     size_t tmp = 0, t2 = 0;
     hipcub::DeviceRadixSort::SortPairs(nullptr, t2, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
@@ -724,23 +730,57 @@ long eap_run(EapScratch** sp, hipStream_t st, const int* d_src, const float* d_m
     tmp = std::max(tmp, t2);
     hipcub::DeviceScan::ExclusiveSum(nullptr, t2, (int*)nullptr, (int*)nullptr, Ki, st);
     tmp = std::max(tmp, t2);
-    if (ensure(eap_carve(nullptr, K, n, tmp, nullptr))) {
+    if (eap_ensure(S, eap_carve(nullptr, K, n, tmp, nullptr))) {
         err = "expected map: out of device memory";
         return -1;
     }
+    eap_carve((char*)S.buf, K, n, tmp, B);
+    *tmp_bytes = tmp;
+    return 0;
+}
+
+static long eap_reduce(EapScratch& S, hipStream_t st, const EapBufs& B, size_t tmp, long K, unsigned int lam_bits,
+                       unsigned int nonfinite, float T, phd_gaussian2d* out, long out_cap, int* n_groups,
+                       std::string& err);
+
+/* Expected map of the current store into host `out` (out_cap entries).
+ * Returns the component count (also when it exceeds out_cap: nothing is then
+ * copied), or -1 on a HIP error (err).  *n_groups = independent groups.
+ * Two stages: collect (sizes, offsets, k_eap_gather: the weighted 7 x K SoA,
+ * the Λ bits and the non-finite flag) and reduce (eap_reduce: everything from
+ * the priority sort on, for any prepared SoA — the sharded form's too). */
+long eap_run(EapScratch** sp, hipStream_t st, const int* d_src, const float* d_map, const int* d_size,
+             const float* d_map_x, const int* d_size_x, const float* d_logw, int n, int cap, float T,
+             phd_gaussian2d* out, long out_cap, int* n_groups, std::string& err) {
+    if (!*sp) *sp = new EapScratch();
+    EapScratch& S = **sp;
+    if (n_groups) *n_groups = 0;
+    // collect: component counts -> offsets (one read-back of n ints)
+    const long K = eap_offsets(S, st, d_src, d_size, d_size_x, n, err);
+    if (K <= 0) return K;
     EapBufs B;
-    eap_carve((char*)S.buf, K, n, tmp, &B);
-    size_t tb;
-    EAPCHK(hipMemcpyAsync(B.off, off.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    size_t tmp = 0;
+    if (eap_scratch(S, st, K, n, &B, &tmp, err)) return -1;
+    EAPCHK(hipMemcpyAsync(B.off, S.off.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice, st));
     EAPCHK(hipMemsetAsync(B.misc, 0, 8 * sizeof(unsigned int), st));
     hipLaunchKernelGGL(k_eap_gather, dim3(n), dim3(256), 0, st, d_src, d_map, d_map_x, B.off, d_logw, cap, K, B.comp,
                        B.misc, (int*)B.misc + 1);
     unsigned int misc[2];
     EAPCHK(hipMemcpyAsync(misc, B.misc, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
     EAPCHK(hipStreamSynchronize(st));
+    return eap_reduce(S, st, B, tmp, K, misc[0], misc[1], T, out, out_cap, n_groups, err);
+}
+
+/* The reduce stage: B.comp holds the weighted 7 x K SoA (concatenation order),
+ * B.misc is zeroed; lam_bits / nonfinite are the set's Λ and flag. */
+static long eap_reduce(EapScratch& S, hipStream_t st, const EapBufs& B, size_t tmp, long K, unsigned int lam_bits,
+                       unsigned int nonfinite, float T, phd_gaussian2d* out, long out_cap, int* n_groups,
+                       std::string& err) {
+    const int Ki = (int)K;
+    size_t tb;
     float lam;
-    memcpy(&lam, &misc[0], 4);
-    const bool one_group = misc[1] != 0 || !(lam > 0.f) || !(lam < INFINITY) || !(T > 0.f) || !(T < INFINITY);
+    memcpy(&lam, &lam_bits, 4);
+    const bool one_group = nonfinite != 0 || !(lam > 0.f) || !(lam < INFINITY) || !(T > 0.f) || !(T < INFINITY);
     const unsigned int nb = (unsigned int)((K + 255) / 256);
     // priority: weight descending, concatenation index ascending (stable sort of the identity)
     hipLaunchKernelGGL(k_iota_u32, dim3(nb), dim3(256), 0, st, B.i0, K);
@@ -872,6 +912,200 @@ long eap_run(EapScratch** sp, hipStream_t st, const int* d_src, const float* d_m
     EAPCHK(hipMemcpyAsync(out, B.g, (size_t)nout * sizeof(phd_gaussian2d), hipMemcpyDeviceToHost, st));
     EAPCHK(hipStreamSynchronize(st));
     return nout;
+}
+
+
+/* ------------------------------------------------- the sharded form (blocks)
+ * Every rank packs its weighted components into a block (header | 7 fields of
+ * stride K_max: the layout in include/phd_capi.h), the caller all-gathers the
+ * blocks in rank order, and every rank concatenates them into the SoA the
+ * single context of all the particles gathers, then runs the same reduce. */
+
+/* the block's header: count, n, layout, stride; Λ bits and flag zeroed (k_eap_gather's atomics fill them) */
+__global__ void k_eap_block_head(unsigned int* __restrict__ head, unsigned int K_r, unsigned int n,
+                                 unsigned int K_max) {
+    const int t = threadIdx.x;
+    unsigned int v = 0;
+    if (t == EAP_BH_LAYOUT) v = EAP_BLOCK_LAYOUT;
+    if (t == EAP_BH_COUNT) v = K_r;
+    if (t == EAP_BH_N) v = n;
+    if (t == EAP_BH_KMAX) v = K_max;
+    if (t < EAP_BH_WORDS) head[t] = v;
+}
+
+/* The gathered headers (one workgroup): every header checked (layout word, n,
+ * stride, K_r <= K_max; a refused header counts no component), the counts
+ * exclusive-scanned into off[world + 1] (rank order), Λ the maximum and the
+ * non-finite flag the OR over the headers.  sum: EAP_HS_* words. */
+__global__ void __launch_bounds__(256)
+    k_eap_block_heads(const unsigned int* __restrict__ blocks, size_t stride_words, int world, unsigned int n,
+                      unsigned int K_max, int* __restrict__ off, unsigned int* __restrict__ sum) {
+    __shared__ unsigned int s_cnt[EAP_MAX_WORLD];
+    __shared__ unsigned int s_lam, s_bad, s_refused;
+    if (threadIdx.x == 0) {
+        s_lam = 0u;
+        s_bad = 0u;
+        s_refused = 0xffffffffu;
+    }
+    __syncthreads();
+    for (int r = threadIdx.x; r < world; r += blockDim.x) {
+        const unsigned int* h = blocks + (size_t)r * stride_words;
+        const unsigned int kr = h[EAP_BH_COUNT];
+        unsigned int why = 0u;
+        if (h[EAP_BH_LAYOUT] != EAP_BLOCK_LAYOUT || h[EAP_BH_KMAX] != K_max) why = EAP_REFUSED_LAYOUT;
+        else if (h[EAP_BH_N] != n) why = EAP_REFUSED_N;
+        else if (kr > K_max) why = EAP_REFUSED_COUNT;
+        s_cnt[r] = why ? 0u : kr;
+        if (why) {
+            atomicMin(&s_refused, (unsigned int)r * 4u + why);  // the first refused rank and its reason
+        } else {
+            atomicMax(&s_lam, h[EAP_BH_LAM]);  // positive floats order as their bit patterns
+            if (h[EAP_BH_BAD]) atomicOr(&s_bad, 1u);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t = 0ull;
+        for (int r = 0; r < world; r++) {
+            off[r] = (int)(t < 0x7fffffffull ? t : 0x7fffffffull);
+            t += s_cnt[r];
+        }
+        off[world] = (int)(t < 0x7fffffffull ? t : 0x7fffffffull);
+        sum[EAP_HS_REFUSED] = s_refused;
+        sum[EAP_HS_LAM] = s_lam;
+        sum[EAP_HS_BAD] = s_bad;
+        sum[EAP_HS_TOTAL_LO] = (unsigned int)t;
+        sum[EAP_HS_TOTAL_HI] = (unsigned int)(t >> 32);
+    }
+}
+
+/* Concatenate: field f (blockIdx.y) of rank r's block (blockIdx.z), K_r floats
+ * at stride K_max behind the header, to comp[f K + off[r] ..): coalesced, 16 B
+ * per lane where source and destination share their alignment (a scalar head
+ * up to the first 16-byte boundary and a scalar tail), else 4 B per lane. */
+__global__ void __launch_bounds__(256)
+    k_eap_concat(const unsigned int* __restrict__ blocks, size_t stride_words, long K_max, const int* __restrict__ off,
+                 long K, float* __restrict__ comp) {
+    const int r = blockIdx.z, f = blockIdx.y;
+    const long o = off[r], kr = (long)off[r + 1] - o;
+    if (kr <= 0) return;
+    const float* src = (const float*)(blocks + (size_t)r * stride_words + EAP_BH_WORDS) + (size_t)f * K_max;
+    float* dst = comp + (size_t)f * K + o;
+    const long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x, nt = (long)gridDim.x * blockDim.x;
+    const unsigned int sa = (unsigned int)(((uintptr_t)src >> 2) & 3u), da = (unsigned int)(((uintptr_t)dst >> 2) & 3u);
+    if (sa != da) {
+        for (long i = t0; i < kr; i += nt) dst[i] = src[i];
+        return;
+    }
+    const long lead = (long)((4u - sa) & 3u);
+    const long head = kr < lead ? kr : lead;
+    const long nv = (kr - head) >> 2;
+    const float4* s4 = (const float4*)(src + head);
+    float4* d4 = (float4*)(dst + head);
+    for (long i = t0; i < nv; i += nt) d4[i] = s4[i];
+    if (blockIdx.x == 0) {  // the few elements before and after the 16-byte body
+        const long tail0 = head + 4 * nv;
+        if ((long)threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
+        if (tail0 + (long)threadIdx.x < kr) dst[tail0 + threadIdx.x] = src[tail0 + threadIdx.x];
+    }
+}
+
+size_t eap_block_bytes(long K_max) {
+    const size_t b = (size_t)EAP_BH_WORDS * 4 + (size_t)28 * (size_t)K_max;
+    return (b + 15) & ~(size_t)15;
+}
+
+/* Component count of the store (what this rank's block will hold), or -1. */
+long eap_shard_count(EapScratch** sp, hipStream_t st, const int* d_src, const int* d_size, const int* d_size_x, int n,
+                     std::string& err) {
+    if (!*sp) *sp = new EapScratch();
+    return eap_offsets(**sp, st, d_src, d_size, d_size_x, n, err);
+}
+
+/* This rank's block: the collect stage with k_eap_gather aimed at the block
+ * (stride K_max, Λ bits and flag in the header).  0, -1 on a HIP error, -2 when
+ * the store holds more than K_max components (nothing is then written). */
+int eap_shard_pack(EapScratch** sp, hipStream_t st, const int* d_src, const float* d_map, const int* d_size,
+                   const float* d_map_x, const int* d_size_x, const float* d_logw, int n, int cap, long K_max,
+                   void* d_block, std::string& err) {
+    if (!*sp) *sp = new EapScratch();
+    EapScratch& S = **sp;
+    const long K_r = eap_offsets(S, st, d_src, d_size, d_size_x, n, err);
+    if (K_r < 0) return -1;
+    if (K_r > K_max) {
+        err = "the store holds " + std::to_string(K_r) + " components, K_max is " + std::to_string(K_max);
+        return -2;
+    }
+    unsigned int* head = (unsigned int*)d_block;
+    hipLaunchKernelGGL(k_eap_block_head, dim3(1), dim3(64), 0, st, head, (unsigned int)K_r, (unsigned int)n,
+                       (unsigned int)K_max);
+    if (K_r > 0) {
+        // (the stream is idle since eap_offsets' read-back: the pinned copy of the previous
+        // pack is consumed, and the sizes' buffer is free to take the offsets)
+        if (S.pin_off_n < n + 1) {
+            if (S.pin_off) hipHostFree(S.pin_off);
+            S.pin_off = nullptr;
+            S.pin_off_n = 0;
+            EAPCHK(hipHostMalloc((void**)&S.pin_off, (size_t)(n + 1) * sizeof(int), hipHostMallocDefault));
+            S.pin_off_n = n + 1;
+        }
+        memcpy(S.pin_off, S.off.data(), (size_t)(n + 1) * sizeof(int));
+        int* d_off = (int*)S.buf;
+        EAPCHK(hipMemcpyAsync(d_off, S.pin_off, (n + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_eap_gather, dim3(n), dim3(256), 0, st, d_src, d_map, d_map_x, d_off, d_logw, cap, K_max,
+                           (float*)(head + EAP_BH_WORDS), head + EAP_BH_LAM, (int*)head + EAP_BH_BAD);
+    }
+    EAPCHK(hipGetLastError());
+    return 0;
+}
+
+/* Expected map of `world` gathered blocks (rank order) into host `out`: the
+ * headers checked and scanned on the device, the blocks concatenated into the
+ * single context's SoA, then eap_run's reduce stage.  Returns as eap_run; -2
+ * when a header is refused (err names the rank; no block is read past its
+ * header). */
+long eap_run_blocks(EapScratch** sp, hipStream_t st, const void* d_blocks, int world, int n, long K_max, float T,
+                    phd_gaussian2d* out, long out_cap, int* n_groups, std::string& err) {
+    if (!*sp) *sp = new EapScratch();
+    EapScratch& S = **sp;
+    if (n_groups) *n_groups = 0;
+    if (S.heads_world < world) {
+        if (S.heads) hipFree(S.heads);
+        S.heads = nullptr;
+        S.heads_world = 0;
+        EAPCHK(hipMalloc((void**)&S.heads, (size_t)(world + 1 + EAP_HS_WORDS) * sizeof(int)));
+        S.heads_world = world;
+    }
+    int* d_off = S.heads;
+    unsigned int* d_sum = (unsigned int*)(S.heads + world + 1);
+    const size_t stride_words = eap_block_bytes(K_max) / 4;
+    hipLaunchKernelGGL(k_eap_block_heads, dim3(1), dim3(256), 0, st, (const unsigned int*)d_blocks, stride_words, world,
+                       (unsigned int)n, (unsigned int)K_max, d_off, d_sum);
+    unsigned int sum[EAP_HS_WORDS];
+    EAPCHK(hipMemcpyAsync(sum, d_sum, sizeof(sum), hipMemcpyDeviceToHost, st));
+    EAPCHK(hipStreamSynchronize(st));
+    if (sum[EAP_HS_REFUSED] != 0xffffffffu) {
+        static const char* const why[] = {"", "its layout word or stride does not match", "its particle count does not match",
+                                          "its component count exceeds K_max"};
+        err = "the block of rank " + std::to_string(sum[EAP_HS_REFUSED] / 4u) + " is refused: " + why[sum[EAP_HS_REFUSED] & 3u];
+        return -2;
+    }
+    const unsigned long long total = ((unsigned long long)sum[EAP_HS_TOTAL_HI] << 32) | sum[EAP_HS_TOTAL_LO];
+    if (total == 0) return 0;
+    if (total >= (1ull << 31) - 1) {
+        err = "expected map: more than 2^31 components";
+        return -1;
+    }
+    const long K = (long)total;
+    EapBufs B;
+    size_t tmp = 0;
+    if (eap_scratch(S, st, K, world, &B, &tmp, err)) return -1;
+    EAPCHK(hipMemsetAsync(B.misc, 0, 8 * sizeof(unsigned int), st));
+    const unsigned int gx = (unsigned int)std::min<long>(std::max<long>((K_max + 1023) / 1024, 1), 4096);
+    hipLaunchKernelGGL(k_eap_concat, dim3(gx, 7, world), dim3(256), 0, st, (const unsigned int*)d_blocks, stride_words,
+                       K_max, d_off, K, B.comp);
+    EAPCHK(hipGetLastError());
+    return eap_reduce(S, st, B, tmp, K, sum[EAP_HS_LAM], sum[EAP_HS_BAD], T, out, out_cap, n_groups, err);
 }
 
 }  // namespace phd

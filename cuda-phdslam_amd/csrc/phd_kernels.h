@@ -557,5 +557,32 @@ void eap_free(EapScratch* s);
 long eap_run(EapScratch** sp, hipStream_t st, const int* d_src, const float* d_map, const int* d_size,
              const float* d_map_x, const int* d_size_x, const float* d_logw, int n, int cap, float T,
              phd_gaussian2d* out, long out_cap, int* n_groups, std::string& err);
+/* the sharded form: a rank's block (layout: include/phd_capi.h) and the reduce of the gathered blocks */
+#define EAP_BLOCK_LAYOUT 0x31504145u /* "EAP1": 64-byte header, 7 float fields of stride K_max */
+#define EAP_BH_WORDS 16   /* header words */
+#define EAP_BH_LAYOUT 0
+#define EAP_BH_COUNT 1    /* K_r */
+#define EAP_BH_LAM 2      /* Λ bits of the rank's components */
+#define EAP_BH_BAD 3      /* non-finite flag */
+#define EAP_BH_N 4        /* particles of the rank */
+#define EAP_BH_KMAX 5     /* the stride the fields were written with */
+#define EAP_MAX_WORLD 1024
+#define EAP_HS_WORDS 8    /* k_eap_block_heads' summary */
+#define EAP_HS_REFUSED 0  /* 0xffffffff, or 4 x rank + EAP_REFUSED_* of the first refused header */
+#define EAP_HS_LAM 1
+#define EAP_HS_BAD 2
+#define EAP_HS_TOTAL_LO 3
+#define EAP_HS_TOTAL_HI 4
+#define EAP_REFUSED_LAYOUT 1
+#define EAP_REFUSED_N 2
+#define EAP_REFUSED_COUNT 3
+size_t eap_block_bytes(long K_max);
+long eap_shard_count(EapScratch** sp, hipStream_t st, const int* d_src, const int* d_size, const int* d_size_x, int n,
+                     std::string& err);
+int eap_shard_pack(EapScratch** sp, hipStream_t st, const int* d_src, const float* d_map, const int* d_size,
+                   const float* d_map_x, const int* d_size_x, const float* d_logw, int n, int cap, long K_max,
+                   void* d_block, std::string& err);
+long eap_run_blocks(EapScratch** sp, hipStream_t st, const void* d_blocks, int world, int n, long K_max, float T,
+                    phd_gaussian2d* out, long out_cap, int* n_groups, std::string& err);
 
 }  // namespace phd

@@ -228,6 +228,7 @@ class ShardedFilter:
         # update's part C (its log-weights are final after the CPHD terms / the
         # split PHD part A: phd_wait_logw); the pack waits for the plan
         self.trace_block = self.trace_blocks = None  # enable_trace
+        self.eap_block = self.eap_blocks = None  # eap_pack
         self.aux = None
         if overlap and f.update_form():
             self.aux = torch.cuda.Stream(device=device, priority=-1)
@@ -331,6 +332,59 @@ class ShardedFilter:
         (which normalises w_all in place)."""
         self.f.trace_shard_append(self.w_all.data_ptr(), self.trace_blocks.data_ptr(), self.world, self.rank)
 
+    # -- the EAP expected map of the whole filter (phd_capi.h) -------------
+    def eap_count(self):
+        """This rank's component count (the store settled: after flush())."""
+        return self.f.eap_shard_count()
+
+    def eap_pack(self, k_max):
+        """This rank's block for the stride k_max (the largest count over the
+        ranks) into eap_block; eap_blocks takes the all-gather of the blocks."""
+        import ctypes
+        import torch
+        from . import _lib
+        nbytes = ctypes.c_size_t()
+        _lib.check(_lib.lib().phd_eap_shard_block_bytes(int(k_max), ctypes.byref(nbytes)), "phd_eap_shard_block_bytes")
+        if self.eap_block is None or self.eap_block.numel() != nbytes.value:
+            self.eap_block = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+            self.eap_blocks = torch.empty(self.world * nbytes.value, dtype=torch.uint8, device=self.device)
+        self.f.eap_shard_pack(k_max, self.eap_block.data_ptr())
+
+    def eap_finish(self, k_max, out_cap, blocks=None, world=None):
+        """After the all-gather of the blocks (rank order) into eap_blocks: the
+        expected map, reduced on this rank.  out_cap: the sum of the counts."""
+        import ctypes
+        from . import _lib
+        blocks = self.eap_blocks if blocks is None else blocks
+        world = self.world if world is None else int(world)
+        nbytes = ctypes.c_size_t()
+        _lib.check(_lib.lib().phd_eap_shard_block_bytes(int(k_max), ctypes.byref(nbytes)), "phd_eap_shard_block_bytes")
+        if blocks is None or blocks.numel() != world * nbytes.value:
+            raise _lib.PHDError(_lib.PHD_E_ARG, "ShardedFilter.eap_finish",
+                                f"{world} blocks of k_max {k_max} are {world * nbytes.value} bytes, the buffer holds "
+                                f"{0 if blocks is None else blocks.numel()}")
+        return self.f.expected_map_blocks(blocks.data_ptr(), world, k_max, out_cap)
+
+    def expected_map(self):
+        """The EAP expected map of all world * n particles, on every rank: what
+        PHDFilter.expected_map returns on a single context holding the ranks'
+        settled stores in rank order, bit for bit.  Settles the open plan
+        (flush), all-gathers the component counts, packs this rank's block,
+        all-gathers the blocks and reduces them locally."""
+        import torch
+        self.flush()
+        mine = torch.tensor([self.eap_count()], dtype=torch.int64, device=self.device)
+        counts = torch.empty(self.world, dtype=torch.int64, device=self.device)
+        self.comm.all_gather(counts, mine)
+        counts = [int(c) for c in counts.tolist()]
+        self.eap_pack(max(counts))
+        self.comm.all_gather(self.eap_blocks, self.eap_block)
+        return self.eap_finish(max(counts), sum(counts))
+
+    def expected_map_groups(self):
+        """Decision rounds of the last expected_map (the single context's)."""
+        return self.f.expected_map_groups()
+
     def receive(self):
         """After the all-to-all of the blocks into recv_blocks."""
         self.f.shard_receive_blocks(self.recv_blocks.data_ptr(), self.K, self.recv_rec.data_ptr())
@@ -422,6 +476,22 @@ class GroupRank:
     def flush(self):
         _group_check(self.L, self.L.phd_group_flush(self._g), "phd_group_flush")
 
+    def expected_map(self):
+        """phd_group_expected_map: as ShardedFilter.expected_map (settles the
+        open plan first; every rank calls it and receives the same map)."""
+        import ctypes
+        import numpy as np
+        from .types import GAUSSIAN2D
+        cap = self.world * self.n * int(self.f.capacity.map_capacity)
+        out = np.zeros(max(cap, 1), GAUSSIAN2D)
+        nout = ctypes.c_long()
+        _group_check(self.L, self.L.phd_group_expected_map(self._g, out.ctypes.data_as(ctypes.c_void_p), cap,
+                                                           ctypes.byref(nout)), "phd_group_expected_map")
+        return out[:nout.value].copy()
+
+    def expected_map_groups(self):
+        return self.f.expected_map_groups()
+
     @property
     def stats(self):
         import ctypes
@@ -458,6 +528,7 @@ def group_lib():
         L.phd_group_step.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_float),
                                      ctypes.POINTER(ctypes.c_int)]
         L.phd_group_flush.argtypes = [vp]
+        L.phd_group_expected_map.argtypes = [vp, vp, ctypes.c_long, ctypes.POINTER(ctypes.c_long)]
         L.phd_group_trace_enable.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint]
         L.phd_group_stats.argtypes = [vp, vp]
         L.phd_group_destroy.argtypes = [vp]

@@ -484,6 +484,27 @@ class PHDFilter:
                                                      ctypes.c_void_p(dev_blocks_ptr), int(world), int(rank)),
                    "phd_trace_shard_append")
 
+    def eap_shard_count(self):
+        """phd_eap_shard_count: the components this rank's expected-map block will hold."""
+        k = ctypes.c_long()
+        _lib.check(_lib.lib().phd_eap_shard_count(self._h, ctypes.byref(k)), "phd_eap_shard_count")
+        return k.value
+
+    def eap_shard_pack(self, k_max, dev_block_ptr):
+        """phd_eap_shard_pack: this rank's weighted components into a device block."""
+        _lib.check(_lib.lib().phd_eap_shard_pack(self._h, int(k_max), ctypes.c_void_p(dev_block_ptr)),
+                   "phd_eap_shard_pack")
+
+    def expected_map_blocks(self, dev_blocks_ptr, world, k_max, out_cap):
+        """phd_expected_map_blocks: the expected map of `world` gathered blocks
+        (out_cap: the total component count always suffices)."""
+        nout = ctypes.c_long()
+        out = np.zeros(max(int(out_cap), 1), GAUSSIAN2D)
+        _lib.check(_lib.lib().phd_expected_map_blocks(self._h, ctypes.c_void_p(dev_blocks_ptr), int(world), int(k_max),
+                                                      _ptr(out), int(out_cap), ctypes.byref(nout)),
+                   "phd_expected_map_blocks")
+        return out[:nout.value]
+
     def update_pending(self, control, step, dev_logw_out_ptr=None, do_predict=True):
         u = ctypes.byref(AckermanControl(float(control[1]), float(control[0]))) if control is not None else None
         _lib.check(_lib.lib().phd_update_pending(self._h, u, 1 if do_predict else 0, int(step),

@@ -314,6 +314,60 @@ int phd_expected_map_dynamic(phd_ctx* ctx, phd_gaussian4d* out, long out_cap, lo
  * the single-workgroup fallback of non-finite inputs). */
 int phd_expected_map_groups(phd_ctx* ctx, int* groups);
 
+/* ---- the EAP expected map of a sharded filter ----
+ * The greedy of phd_expected_map is global (the first seed is the heaviest
+ * weighted component over every rank, ties break by concatenation index, a
+ * lattice cell's decisions wait on its neighbours), so per-rank maps do not
+ * merge into it.  As for the sharded trace, the inputs travel: every rank packs
+ * its weighted components into a block, the caller all-gathers the blocks in
+ * rank order, and every rank reduces the whole set with phd_expected_map's own
+ * reduce stage.  Every rank then holds, bit for bit and in the same emission
+ * order, what phd_expected_map returns on a single context of world * n
+ * particles loaded with the ranks' settled stores in rank order (rank 0's slots
+ * 0 .. n-1, then rank 1's, ...; each particle's components in slab order, its
+ * log-weight as stored); phd_expected_map_groups reports the same rounds.
+ *
+ * The block (phd_eap_shard_block_bytes: 64 + 28 K_max bytes rounded up to 16):
+ *     bytes 0 .. 63   header, 16 x uint32: [0] layout word 0x31504145 ("EAP1")
+ *                     [1] K_r, this rank's component count  [2] the bits of Λ,
+ *                     the largest covariance eigenvalue of the rank's components
+ *                     [3] non-finite flag  [4] n  [5] K_max (the fields' stride)
+ *                     [6 .. 15] zero
+ *     bytes 64 ..     seven float fields of stride K_max, K_r entries each:
+ *                     weight (exp(log w_p) x component weight, the single
+ *                     context's phd_det_expf product), mean x, mean y, cov 00,
+ *                     10, 01, 11; particles in slot order, components in slab
+ *                     order.  Entries K_r .. K_max-1 are never read.
+ * K_max is the largest K_r over the ranks (any larger value gives the same
+ * result).  Per call the caller makes, with the plan settled (phd_shard_poll ..
+ * phd_update_pending done: the store final):
+ *     phd_eap_shard_count(ctx, &K_r);  all-gather of the counts;  K_max = max
+ *     phd_eap_shard_pack(ctx, K_max, dev_block);
+ *     all-gather of dev_block into dev_blocks (rank order), on the context stream;
+ *     phd_expected_map_blocks(ctx, dev_blocks, world, K_max, out, out_cap, &n_out);
+ * phd_eap_shard_count synchronises (one read-back of n ints).
+ * phd_eap_shard_pack reads the slabs through the slab references (migrated
+ * slabs included) and enqueues the block's kernels on the context stream; it
+ * makes the same read-back first, and returns PHD_E_ARG (nothing written) when
+ * the store holds more than K_max components.  dev_block / dev_blocks are
+ * 16-byte aligned.  phd_expected_map_blocks reads the headers on the device
+ * (Λ: the maximum, the flag: the OR, the counts scanned into rank-ordered
+ * offsets), concatenates the blocks into one SoA of Σ K_r components and
+ * reduces it on this context's scratch and stream; out / out_cap / n_out and
+ * T = minSeparation as phd_expected_map, n_out <= Σ K_r.  It synchronises.
+ * PHD_E_ARG, before any field is read: a header whose K_r exceeds K_max, or
+ * whose n, layout word or stride differs from this call's; world outside
+ * [1, 1024]; world blocks that do not fit the allocation dev_blocks points
+ * into.  Every rank reduces the whole set (as every rank computes the whole
+ * plan): about 230 bytes of scratch per component per rank.
+ * PHD_E_UNSUPPORTED: feature_model != 0, as the sharded step.
+ * phd_eap_shard_block_bytes is pure arithmetic (no device). */
+int phd_eap_shard_count(phd_ctx* ctx, long* K_local);
+int phd_eap_shard_block_bytes(long K_max, size_t* bytes);
+int phd_eap_shard_pack(phd_ctx* ctx, long K_max, void* dev_block);
+int phd_expected_map_blocks(phd_ctx* ctx, const void* dev_blocks, int world, long K_max, phd_gaussian2d* out,
+                            long out_cap, long* n_out);
+
 /* ---- per-scan estimate trace on the device ----
  * With the trace on, every phd_step appends one phd_trace_record (phd_types.h)
  * to a device ring: the estimates the synchronous entry points above return

@@ -74,6 +74,17 @@ int phd_group_step(phd_group* g, const phd_ackerman_control* u, uint64_t step, f
 int phd_group_trace_enable(phd_group* g, int capacity, int map_snapshot_cap, unsigned flags);
 /* Settle the last plan (no update follows): the contexts' stores are final. */
 int phd_group_flush(phd_group* g);
+/* The EAP expected map of the whole filter (phd_capi.h: "the EAP expected map
+ * of a sharded filter"): what phd_expected_map returns on a single context of
+ * all world * n particles in rank order, bit for bit.  Settles the open plan
+ * (as phd_group_flush), ncclAllGather of the ranks' component counts, K_max
+ * their maximum, phd_eap_shard_pack, one ncclAllGather of the blocks, and
+ * phd_expected_map_blocks on every rank of this process; out / out_cap / n_out
+ * as phd_expected_map (rank 0's copy in the one-process form; every process
+ * of the phd_group_create_rank form calls it and receives the same map).
+ * The blocks are allocated here, 28 K_max + 64 bytes per rank, and kept.
+ * Synchronises. */
+int phd_group_expected_map(phd_group* g, phd_gaussian2d* out, long out_cap, long* n_out);
 /* Counters over the steps so far: [0] resamples, [1] migrated particles,
  * [2] records sent, [3] records beyond the fixed blocks, [4] pending slots. */
 int phd_group_stats(const phd_group* g, long long* out5);
