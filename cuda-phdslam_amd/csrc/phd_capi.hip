@@ -204,6 +204,13 @@ struct phd_ctx {
         int* d_hand = nullptr;
         float* d_card_row = nullptr;  // sharded trace: the arg-max particle's row before it is packed
         bool shard_packed = false;    // phd_trace_shard_pack enqueued, its phd_trace_shard_append not yet
+        // mixed-model trace (phd_trace_enable_mixed): the parallel dyn ring, the
+        // dynamic snapshots and the dynamic capacity it was enabled with
+        bool mixed = false;
+        int dsnap_cap = 0, dcap = 0;
+        phd_trace_dyn_record* d_drec = nullptr;
+        phd_gaussian4d* d_dsnap = nullptr;
+        double* d_dpart = nullptr;
     } tr;
     hipEvent_t ev_trace = nullptr;  // sharded trace: the gathered log-weights (plan stream) before the pack
 };
@@ -408,7 +415,7 @@ static ZBlk zblk_layout() {
 
 static void trace_free(phd_ctx* c) {
     void* ptrs[] = {c->tr.d_rec, c->tr.d_snap, c->tr.d_card, c->tr.d_card_all, c->tr.d_w, c->tr.d_part, c->tr.d_hand,
-                    c->tr.d_card_row};
+                    c->tr.d_card_row, c->tr.d_drec, c->tr.d_dsnap, c->tr.d_dpart};
     for (void* p : ptrs)
         if (p) hipFree(p);
     c->tr = {};
@@ -1889,7 +1896,16 @@ int phd_predict_update(phd_ctx* ctx, const phd_ackerman_control* u, int do_predi
  * phd_trace_enable asks for neither: the context may serve either step. */
 enum TraceUse { TRACE_ENABLE, TRACE_STEP, TRACE_SHARDED };
 static int trace_supported(const phd_ctx* ctx, TraceUse use) {
-    if (ctx->cfg.featureModel != PHD_FEATURE_STATIC)
+    if (ctx->tr.mixed) {
+        // a mixed-model trace (phd_trace_enable_mixed): the model and the dynamic
+        // capacity its rings and launches were sized for
+        if (ctx->cfg.featureModel != PHD_FEATURE_MIXED)
+            return fail(PHD_E_UNSUPPORTED,
+                        "feature_model changed after phd_trace_enable_mixed: enable the trace again");
+        if (!ctx->dyn || ctx->dcap != ctx->tr.dcap)
+            return fail(PHD_E_UNSUPPORTED,
+                        "the dynamic capacity changed after phd_trace_enable_mixed: enable the trace again");
+    } else if (ctx->cfg.featureModel != PHD_FEATURE_STATIC)
         return fail(PHD_E_UNSUPPORTED, "the estimate trace supports the static feature model only");
     if (ctx->cfg.nPredictParticles > 1 || ctx->n != ctx->n_base)
         return fail(PHD_E_UNSUPPORTED, "the estimate trace does not support n_predict_particles > 1");
@@ -1934,6 +1950,15 @@ static int trace_append(phd_ctx* ctx, uint64_t step) {
     a.snap = T.d_snap ? T.d_snap + slot * (size_t)T.snap_cap : nullptr;
     a.snap_cap = T.snap_cap;
     a.K = T.K;
+    if (T.mixed) {  // the dynamic set that is current after the update (or, on an empty scan, the predict)
+        a.dmap = ctx->d_dmap[ctx->dcur];
+        a.dsize = ctx->d_dsize[ctx->dcur];
+        a.dcap = ctx->dcap;
+        a.dpart = T.d_dpart;
+        a.drec = T.d_drec + slot;
+        a.dsnap = T.d_dsnap ? T.d_dsnap + slot * (size_t)T.dsnap_cap : nullptr;
+        a.dsnap_cap = T.dsnap_cap;
+    }
     trace_launch_stage1(a, ctx->stream);
     if (T.d_card && ctx->cn_valid) {
         float* entry = T.d_card + slot * (size_t)T.K;
@@ -1955,15 +1980,30 @@ static int trace_append(phd_ctx* ctx, uint64_t step) {
     return PHD_OK;
 }
 
-int phd_trace_enable(phd_ctx* ctx, int capacity, int map_snapshot_cap, unsigned flags) {
-    if (!ctx || capacity < 0 || map_snapshot_cap < 0) return fail(PHD_E_ARG, "bad arguments to phd_trace_enable");
+/* phd_trace_enable, and with mixed (phd_trace_enable_mixed) the dyn ring beside it */
+static int trace_enable(phd_ctx* ctx, int capacity, int map_snapshot_cap, int dyn_snapshot_cap, unsigned flags,
+                        bool mixed) {
+    const std::string who = mixed ? "phd_trace_enable_mixed" : "phd_trace_enable";
+    if (!ctx || capacity < 0 || map_snapshot_cap < 0 || dyn_snapshot_cap < 0)
+        return fail(PHD_E_ARG, "bad arguments to " + who);
     if (set_device(ctx)) return PHD_E_HIP;
     HIPCHK(hipStreamSynchronize(ctx->stream));
     trace_free(ctx);
     if (capacity == 0) return PHD_OK;
     if (!ctx->cfg_set) return fail(PHD_E_ARG, "phd_set_config not called");
     if (flags & ~(unsigned)PHD_TRACE_CARD_DIST) return fail(PHD_E_ARG, "unknown trace flags");
+    if (mixed) {
+        if (!PHD_TRACE_DYN)
+            return fail(PHD_E_UNSUPPORTED, "this build has the dynamic trace stages compiled out (PHD_TRACE_DYN 0)");
+        if (ctx->cfg.featureModel != PHD_FEATURE_MIXED)
+            return fail(PHD_E_UNSUPPORTED, "phd_trace_enable_mixed needs feature_model 2 (phd_trace_enable serves the static model)");
+        if (!ctx->dyn) return fail(PHD_E_ARG, "phd_trace_enable_mixed: phd_enable_dynamic not called");
+        if (flags & PHD_TRACE_CARD_DIST)
+            return fail(PHD_E_UNSUPPORTED, "PHD_TRACE_CARD_DIST on a mixed trace: feature_model 2 has no CPHD filter");
+    }
     auto& T = ctx->tr;
+    T.mixed = mixed;
+    T.dcap = mixed ? ctx->dcap : 0;
     T.flags = flags;
     T.K = (flags & PHD_TRACE_CARD_DIST) ? ctx->cfg.maxCardinality + 1 : 0;
     int rc = trace_supported(ctx, TRACE_ENABLE);
@@ -1992,14 +2032,32 @@ int phd_trace_enable(phd_ctx* ctx, int capacity, int map_snapshot_cap, unsigned 
     if (e == hipSuccess && T.d_snap)
         e = hipMemsetAsync(T.d_snap, 0, (size_t)capacity * map_snapshot_cap * sizeof(phd_gaussian2d), ctx->stream);
     if (e == hipSuccess && T.d_card) e = hipMemsetAsync(T.d_card, 0, (size_t)capacity * T.K * sizeof(float), ctx->stream);
+    if (mixed) {
+        const size_t dsnap_bytes = (size_t)capacity * dyn_snapshot_cap * sizeof(phd_gaussian4d);
+        if (e == hipSuccess) e = hipMalloc((void**)&T.d_drec, (size_t)capacity * sizeof(phd_trace_dyn_record));
+        if (e == hipSuccess) e = hipMalloc((void**)&T.d_dpart, ((N + TRACE_PB - 1) / TRACE_PB) * sizeof(double));
+        if (e == hipSuccess && dyn_snapshot_cap > 0) e = hipMalloc((void**)&T.d_dsnap, dsnap_bytes);
+        if (e == hipSuccess)
+            e = hipMemsetAsync(T.d_drec, 0, (size_t)capacity * sizeof(phd_trace_dyn_record), ctx->stream);
+        if (e == hipSuccess && T.d_dsnap) e = hipMemsetAsync(T.d_dsnap, 0, dsnap_bytes, ctx->stream);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
         trace_free(ctx);
-        return fail(PHD_E_HIP, std::string("phd_trace_enable: ") + hipGetErrorString(e));
+        return fail(PHD_E_HIP, who + ": " + hipGetErrorString(e));
     }
     T.snap_cap = map_snapshot_cap;
+    T.dsnap_cap = mixed ? dyn_snapshot_cap : 0;
     T.cap = capacity;  // (on from here)
     return PHD_OK;
+}
+
+int phd_trace_enable(phd_ctx* ctx, int capacity, int map_snapshot_cap, unsigned flags) {
+    return trace_enable(ctx, capacity, map_snapshot_cap, 0, flags, false);
+}
+
+int phd_trace_enable_mixed(phd_ctx* ctx, int capacity, int map_snapshot_cap, int dyn_snapshot_cap, unsigned flags) {
+    return trace_enable(ctx, capacity, map_snapshot_cap, dyn_snapshot_cap, flags, true);
 }
 
 int phd_trace_count(phd_ctx* ctx, long* written_total) {
@@ -2032,6 +2090,36 @@ int phd_trace_read(phd_ctx* ctx, long first, int count, phd_trace_record* record
     if (maps) HIPCHK(pull(maps, T.d_snap, (size_t)T.snap_cap * sizeof(phd_gaussian2d)));
     if (card) HIPCHK(pull(card, T.d_card, (size_t)T.K * sizeof(float)));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PHD_OK;
+}
+
+int phd_trace_read_dynamic(phd_ctx* ctx, long first, int count, phd_trace_dyn_record* records, phd_gaussian4d* dmaps) {
+    if (!ctx || count < 0 || (count > 0 && !records)) return fail(PHD_E_ARG, "bad arguments to phd_trace_read_dynamic");
+    const auto& T = ctx->tr;
+    if (T.cap <= 0 || !T.mixed) return fail(PHD_E_ARG, "the mixed estimate trace is off (phd_trace_enable_mixed)");
+    if (first < 0 || first + count > T.count) return fail(PHD_E_ARG, "trace records not written yet");
+    if (first < T.count - T.cap) return fail(PHD_E_ARG, "trace records already overwritten");
+    if (dmaps && !T.d_dsnap) return fail(PHD_E_ARG, "the trace has no dynamic map snapshots");
+    if (count == 0) return PHD_OK;
+    if (set_device(ctx)) return PHD_E_HIP;
+    // the range is one run of the ring, or two where it wraps (as phd_trace_read)
+    const size_t s0 = (size_t)(first % T.cap);
+    const size_t c0 = std::min((size_t)count, (size_t)T.cap - s0), c1 = (size_t)count - c0;
+    auto pull = [&](void* dst, const void* ring, size_t entry) -> hipError_t {
+        hipError_t e = hipMemcpyAsync(dst, (const char*)ring + s0 * entry, c0 * entry, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && c1)
+            e = hipMemcpyAsync((char*)dst + c0 * entry, ring, c1 * entry, hipMemcpyDeviceToHost, ctx->stream);
+        return e;
+    };
+    HIPCHK(pull(records, T.d_drec, sizeof(phd_trace_dyn_record)));
+    if (dmaps) HIPCHK(pull(dmaps, T.d_dsnap, (size_t)T.dsnap_cap * sizeof(phd_gaussian4d)));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PHD_OK;
+}
+
+int phd_trace_shape_dynamic(phd_ctx* ctx, int* dyn_snapshot_cap) {
+    if (!ctx) return fail(PHD_E_ARG, "null ctx");
+    if (dyn_snapshot_cap) *dyn_snapshot_cap = ctx->tr.dsnap_cap;
     return PHD_OK;
 }
 
@@ -2085,6 +2173,9 @@ static int trace_shard_check(phd_ctx* ctx, const void* dev_w_all, const void* de
         (long long)world * ctx->n > (long long)RS_MAX_CHUNKS * RS_THREADS)
         return fail(PHD_E_ARG, std::string("bad arguments to ") + who);
     if (!ctx->cfg_set || ctx->tr.cap <= 0) return fail(PHD_E_ARG, "the estimate trace is off (phd_trace_enable)");
+    if (ctx->tr.mixed)
+        return fail(PHD_E_UNSUPPORTED, std::string(who) + ": a mixed trace (phd_trace_enable_mixed) — the sharded step "
+                                       "does not support feature_model 2");
     return PHD_OK;
 }
 

@@ -15,6 +15,14 @@ namespace phd {
 /* particles per workgroup of the cardinality stage (4 waves, 8 particles each) */
 #define TRACE_PB 32
 
+/* 1: the dynamic half of the mixed-model trace (phd_trace_enable_mixed) is
+ * compiled in; 0 leaves the static trace's kernels as they were without it */
+#ifndef PHD_TRACE_DYN
+#define PHD_TRACE_DYN 1
+#endif
+/* dynamic components per workgroup of the snapshot transpose (4 waves, one strip of 64 each) */
+#define TRACE_DSNAP_PB 256
+
 /* scratch words the stages hand each other (TraceArgs::hand) */
 #define TRACE_H_PARTICLE 0 /* arg-max particle */
 #define TRACE_H_SLAB 1     /* its slab reference (src[particle]) */
@@ -50,12 +58,24 @@ struct TraceArgs {
     float* card;
     const float* card_all;
     int K;
+    /* the dynamic half of a mixed-model scan (dmap NULL: a static trace): the
+     * dynamic slab set that is current after the update, [w | m0..m3 | c0..c15]
+     * x dcap per slab, addressed by the same slab references as the static set */
+    const float* dmap;
+    const int* dsize;
+    int dcap;
+    double* dpart;             /* ceil(n / TRACE_PB) partial sums of the dynamic card_expected */
+    phd_trace_dyn_record* drec; /* this scan's entry of the dyn ring */
+    phd_gaussian4d* dsnap;      /* NULL: no dynamic snapshot */
+    int dsnap_cap;
 };
 
 /* Stage 1 (weights final, parents not applied): one 1024-thread workgroup. */
 void trace_launch_stage1(const TraceArgs& a, hipStream_t st);
 /* Stage 2 (posterior maps written): cardinalities by blocks of particles, then
- * the fixed-order combine, the snapshot and the expected cardinality rows. */
+ * the fixed-order combine, the snapshot and the expected cardinality rows; with
+ * a.dmap set also the dynamic half (same grid of k_trace_card, 1 + ceil(dsnap_cap
+ * / TRACE_DSNAP_PB) more workgroups of k_trace_finish). */
 void trace_launch_stage2(const TraceArgs& a, hipStream_t st);
 
 /* ---- the trace of a sharded step (phd_trace_shard_pack / _append, phd_capi.h) ----

@@ -15,6 +15,12 @@
  *            each map by one wave (k_cardinality's sum), weighted partials
  *            k_trace_finish    the fixed-order combine, the map snapshot and
  *            the expected cardinality rows
+ * The mixed model's trace (phd_trace_enable_mixed, feature_model 2) rides in the
+ * same launches: k_trace_card also sums every particle's dynamic slab (the
+ * weights row of the 21-row SoA slab, through the same slab reference) into a
+ * second set of partials, k_trace_finish gets one more workgroup for their
+ * combine and one per 256 snapshot components for the Gaussian4D transpose.
+ * Stage 1 is shared: one arg-max, one set of normalised weights per scan.
  * The sharded step's trace (phd_trace_shard_pack / _append, below): the same
  * record from all world * n particles — k_trace_shard_weights on the gathered
  * log-weights, k_trace_shard_pack into this rank's block, the caller's
@@ -29,6 +35,7 @@
 #include "phd_device.h"
 #include "phd_devutil.h"
 #include "phd_kernels.h"
+#include "phd_mixed_k.h"
 #include "phd_slab.h"
 #include "phd_trace.h"
 
@@ -84,12 +91,37 @@ __global__ void __launch_bounds__(RS_THREADS) k_trace_weights(TraceArgs a) {
     }
 }
 
+#if PHD_TRACE_DYN
+/* Particle p's dynamic map: slab slab_index(src[p]) of the dynamic set, 21 SoA
+ * rows of dcap floats (the mixed model holds no migrated slabs). */
+__device__ __forceinline__ Slab dyn_slab_of(int sref, const float* dmap, const int* dsize, int dcap) {
+    const int r = slab_index(sref);
+    return Slab{dmap + (size_t)r * PHD_DYN_FIELDS * dcap, dsize[r]};
+}
+#endif
+
+/* The fixed-order combine of nparts partials by one 256-thread workgroup
+ * (thread t takes partials t, t + 256, ...; wave scans; the wave totals in
+ * order): card_expected's rule, for the static and the dynamic maps. */
+__device__ __forceinline__ float combine_partials(const double* part, int nparts, double* s_w) {
+    const int t = threadIdx.x;
+    double v = 0.0;
+    for (int i = t; i < nparts; i += 256) v += part[i];
+    v = wave_incl_scan_d(v);
+    if ((t & 63) == 63) s_w[t >> 6] = v;
+    __syncthreads();
+    return (float)(((s_w[0] + s_w[1]) + s_w[2]) + s_w[3]);
+}
+
 /* Σ_j w_j of TRACE_PB maps per workgroup, one wave per map at a time (the
  * double sum of k_cardinality, rounded to float as phd_cardinalities returns
  * it), times exp(w_n); the workgroup's partial of card_expected is the sum of
  * its particles' terms in index order. */
 __global__ void __launch_bounds__(256) k_trace_card(TraceArgs a) {
     __shared__ double s_term[TRACE_PB];
+#if PHD_TRACE_DYN
+    __shared__ double s_dterm[TRACE_PB];
+#endif
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int base = blockIdx.x * TRACE_PB;
     const int best = a.hand[TRACE_H_PARTICLE];
@@ -111,12 +143,42 @@ __global__ void __launch_bounds__(256) k_trace_card(TraceArgs a) {
         }
         if (lane == 0) s_term[q] = term;
     }
+#if PHD_TRACE_DYN
+    // the same sum over the particles' dynamic slabs (row 0 of a slab: the weights)
+    if (a.dmap)
+        for (int q = wid; q < TRACE_PB; q += 4) {
+            const int p = base + q;
+            double term = 0.0;
+            if (p < a.n) {
+                const Slab m = dyn_slab_of(a.src[p], a.dmap, a.dsize, a.dcap);
+                const int sz = min(max(m.size, 0), a.dcap);
+                double s = 0.0;
+                for (int k = lane; k < sz; k += 64) s += (double)m.map[k];
+                s = wave_sum_d(s);
+                const float cn = (float)s;
+                term = (double)expf(a.w_norm[p]) * (double)cn;
+                if (p == best && lane == 0) {
+                    a.drec->card_map = cn;
+                    a.drec->map_size = sz;
+                    for (int i = 0; i < 5; i++) a.drec->reserved[i] = 0;
+                }
+            }
+            if (lane == 0) s_dterm[q] = term;
+        }
+#endif
     __syncthreads();
     if (threadIdx.x == 0) {
         double s = 0.0;
         for (int q = 0; q < TRACE_PB; q++) s += s_term[q];
         a.part[blockIdx.x] = s;
     }
+#if PHD_TRACE_DYN
+    if (threadIdx.x == 64 && a.dmap) {
+        double s = 0.0;
+        for (int q = 0; q < TRACE_PB; q++) s += s_dterm[q];
+        a.dpart[blockIdx.x] = s;
+    }
+#endif
 }
 
 /* Workgroup 0: the partials of card_expected in a fixed order (thread t takes
@@ -124,17 +186,43 @@ __global__ void __launch_bounds__(256) k_trace_card(TraceArgs a) {
  * Workgroup 1: the arg-max particle's map into the snapshot entry — the entry
  * as a flat run of floats, so consecutive lanes store consecutive words.
  * Workgroup 2: the expected cardinality rows, Σ_n exp(w_n) cn_n[k] in particle
- * order (float, the sum recoverSlamState makes), one thread per k. */
+ * order (float, the sum recoverSlamState makes), one thread per k.
+ * A mixed-model scan adds workgroup 3: the dynamic card_expected from its
+ * partials, workgroup 0's combine; and workgroups 4 onward: the arg-max
+ * particle's dynamic map into the dyn snapshot entry, one wave per strip of 64
+ * components — each field's 64 values in one coalesced load, then every lane
+ * stores its component's whole phd_gaussian4d (zeros past the map's size). */
 __global__ void __launch_bounds__(256) k_trace_finish(TraceArgs a, int nparts) {
     const int t = threadIdx.x;
+    __shared__ double s_w[4];
+#if PHD_TRACE_DYN
+    if (blockIdx.x == 3) {
+        const float ce = combine_partials(a.dpart, nparts, s_w);
+        if (t == 0) a.drec->card_expected = ce;
+        return;
+    }
+    if (blockIdx.x > 3) {
+        const Slab m = dyn_slab_of(a.hand[TRACE_H_SLAB], a.dmap, a.dsize, a.dcap);
+        const int rows = min(min(max(m.size, 0), a.dcap), a.dsnap_cap);
+        const int k = (blockIdx.x - 4) * TRACE_DSNAP_PB + t;  // (a wave's 64 lanes: one strip)
+        if (k >= a.dsnap_cap) return;
+        phd_gaussian4d g;
+        if (k < rows) {
+            g.weight = m.map[k];
+            for (int i = 0; i < 4; i++) g.mean[i] = m.map[(size_t)(1 + i) * a.dcap + k];
+            for (int i = 0; i < 16; i++) g.cov[i] = m.map[(size_t)(5 + i) * a.dcap + k];
+        } else {
+            g.weight = 0.f;
+            for (int i = 0; i < 4; i++) g.mean[i] = 0.f;
+            for (int i = 0; i < 16; i++) g.cov[i] = 0.f;
+        }
+        a.dsnap[k] = g;
+        return;
+    }
+#endif
     if (blockIdx.x == 0) {
-        __shared__ double s_w[4];
-        double v = 0.0;
-        for (int i = t; i < nparts; i += 256) v += a.part[i];
-        v = wave_incl_scan_d(v);
-        if ((t & 63) == 63) s_w[t >> 6] = v;
-        __syncthreads();
-        if (t == 0) a.rec->card_expected = (float)(((s_w[0] + s_w[1]) + s_w[2]) + s_w[3]);
+        const float ce = combine_partials(a.part, nparts, s_w);
+        if (t == 0) a.rec->card_expected = ce;
     } else if (blockIdx.x == 1) {
         if (!a.snap) return;
         const Slab m = slab_of(a.hand[TRACE_H_SLAB], a.map_in, a.size_in, a.map_x, a.size_x, a.cap);
@@ -164,7 +252,11 @@ void trace_launch_stage1(const TraceArgs& a, hipStream_t st) {
 void trace_launch_stage2(const TraceArgs& a, hipStream_t st) {
     const int nparts = (a.n + TRACE_PB - 1) / TRACE_PB;
     hipLaunchKernelGGL(k_trace_card, dim3(nparts), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_trace_finish, dim3(3), dim3(256), 0, st, a, nparts);
+    int finish = 3;
+#if PHD_TRACE_DYN
+    if (a.dmap) finish = 4 + (a.dsnap ? (a.dsnap_cap + TRACE_DSNAP_PB - 1) / TRACE_DSNAP_PB : 0);
+#endif
+    hipLaunchKernelGGL(k_trace_finish, dim3(finish), dim3(256), 0, st, a, nparts);
 }
 
 /* ---- the trace of a sharded step: the record the single context of

@@ -18,11 +18,18 @@
  * --log DIR writes DIR/state_estimateNNNNN.log every step (writeLog,
  * main.cpp:848-954): expected pose, the EAP (mapEstimate & 2) or MAP map,
  * log-weights, poses, resample indices, cardinality.
- * --trace (single GPU, static feature model, n_predict_particles 1) runs the
- * device loop free: phd_set_measurements + phd_step per scan with no read-back,
- * the device-side estimate trace (phd_trace_enable) read once at the end and
- * written to trajectory.txt (in --log DIR, else the working directory), one
- * line per scan: scan, expected pose, MAP pose, nEff, resampled, cardinalities.
+ * --trace (single GPU, static or mixed feature model, n_predict_particles 1)
+ * runs the device loop free: phd_set_measurements + phd_step per scan with no
+ * read-back, the device-side estimate trace (phd_trace_enable) read once at the
+ * end and written to trajectory.txt (in --log DIR, else the working directory),
+ * one line per scan: scan, expected pose, MAP pose, nEff, resampled,
+ * cardinalities.  With feature_model = 2 (dynamic maps of up to 256 components
+ * per particle; measurements.txt then carries labels, --triples) those
+ * cardinalities describe the static maps, and the dynamic half of the trace
+ * (phd_trace_enable_mixed) goes to trajectory_dynamic.txt beside it, one line
+ * per scan: scan, card_expected (Σ_n exp(w_n) Σ_j w_nj over the dynamic maps),
+ * card_map and map_size (the MAP particle's dynamic map: Σ_j w_j and its
+ * component count).
  *
  *   phdslam_run --synth C [--gpus N] [--particles P] [--steps K] [--replay]
  *               [--block-records R] [--resample-every] [--dump FILE]
@@ -345,7 +352,11 @@ int main(int argc, char** argv) {
         if (trace) {
             // the free-running chain: phd_set_measurements + phd_step per scan, no
             // read-back; the estimates come from the device trace, read once
-            if (phd_set_check_each_update(ctx, 0) != PHD_OK || phd_trace_enable(ctx, std::max(nSteps, 1), 0, 0) != PHD_OK) {
+            const bool mixed = config.featureModel == 2;  // PHD_FEATURE_MIXED
+            const int ring = std::max(nSteps, 1);
+            if (phd_set_check_each_update(ctx, 0) != PHD_OK ||
+                (mixed ? phd_enable_dynamic(ctx, 256) != PHD_OK || phd_trace_enable_mixed(ctx, ring, 0, 0, 0) != PHD_OK
+                       : phd_trace_enable(ctx, ring, 0, 0) != PHD_OK)) {
                 fprintf(stderr, "--trace: %s\n", phd_last_error());
                 return 1;
             }
@@ -382,6 +393,24 @@ int main(int argc, char** argv) {
             }
             fclose(fp);
             printf("wrote %s (%d scans)\n", path.c_str(), nSteps);
+            if (mixed) {
+                std::vector<phd_trace_dyn_record> drec((size_t)ring);
+                if (phd_trace_read_dynamic(ctx, 0, nSteps, drec.data(), nullptr) != PHD_OK) {
+                    fprintf(stderr, "--trace: %s\n", phd_last_error());
+                    return 1;
+                }
+                const std::string dpath = (log_dir.empty() ? std::string(".") : log_dir) + "/trajectory_dynamic.txt";
+                fp = fopen(dpath.c_str(), "w");
+                if (!fp) {
+                    fprintf(stderr, "cannot write %s\n", dpath.c_str());
+                    return 1;
+                }
+                fprintf(fp, "%% scan  card_expected  card_map  map_size  (dynamic maps)\n");
+                for (int n = 0; n < nSteps; n++)
+                    fprintf(fp, "%d %.9g %.9g %d\n", n, drec[n].card_expected, drec[n].card_map, drec[n].map_size);
+                fclose(fp);
+                printf("wrote %s (%d scans)\n", dpath.c_str(), nSteps);
+            }
         }
         for (int n = 0; n < nSteps && !trace; n++) {
             AckermanControl u{0.f, 0.f};

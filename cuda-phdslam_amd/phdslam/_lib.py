@@ -96,6 +96,9 @@ SIGNATURES = {
     "phd_trace_count": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_long)]),
     "phd_trace_read": (ctypes.c_int, [_vp, ctypes.c_long, ctypes.c_int, _vp, _vp, _vp]),
     "phd_trace_shape": (ctypes.c_int, [_vp, _c_int_p, _c_int_p, _c_int_p]),
+    "phd_trace_enable_mixed": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint]),
+    "phd_trace_read_dynamic": (ctypes.c_int, [_vp, ctypes.c_long, ctypes.c_int, _vp, _vp]),
+    "phd_trace_shape_dynamic": (ctypes.c_int, [_vp, _c_int_p]),
     "phd_trace_shard_block_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                    ctypes.POINTER(ctypes.c_size_t)]),
     "phd_trace_shard_pack": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _u64, _vp]),

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .types import (ACKERMAN_NOISE, CV_NOISE, GAUSSIAN2D, GAUSSIAN4D, MEASUREMENT, POSE, TRACE_CARD_DIST,
-                    TRACE_RECORD, AckermanControl, Capacity, SlamConfig, csr_from_maps)
+                    TRACE_DYN_RECORD, TRACE_RECORD, AckermanControl, Capacity, SlamConfig, csr_from_maps)
 
 
 def _ptr(a):
@@ -313,6 +313,35 @@ class PHDFilter:
         _lib.check(_lib.lib().phd_trace_read(self._h, int(first), int(count), _ptr(rec), _ptr(maps), _ptr(card)),
                    "phd_trace_read")
         return (rec, maps, card) if (snap or K) else rec
+
+    def enable_trace_mixed(self, capacity, map_snapshot_cap=0, dyn_snapshot_cap=0):
+        """phd_trace_enable_mixed (feature_model 2, after enable_dynamic): what
+        enable_trace turns on — its records describe the static maps — and a
+        parallel ring of TRACE_DYN_RECORD for the dynamic maps; dyn_snapshot_cap >
+        0 also keeps that many GAUSSIAN4D components of the arg-max particle's
+        dynamic map per scan.  capacity 0: off."""
+        _lib.check(_lib.lib().phd_trace_enable_mixed(self._h, int(capacity), int(map_snapshot_cap),
+                                                     int(dyn_snapshot_cap), 0), "phd_trace_enable_mixed")
+
+    def read_trace_dynamic(self, first=None, count=None):
+        """The dyn records [first, first + count) as a TRACE_DYN_RECORD array
+        (default: every scan the ring still holds, as read_trace); with dynamic
+        snapshots enabled returns (records, dmaps[count, dyn_snapshot_cap]
+        GAUSSIAN4D).  One synchronisation."""
+        cap = self.trace_shape()[0]
+        dsnap = ctypes.c_int()
+        _lib.check(_lib.lib().phd_trace_shape_dynamic(self._h, ctypes.byref(dsnap)), "phd_trace_shape_dynamic")
+        dsnap = dsnap.value
+        total = self.trace_count()
+        if first is None:
+            first = max(0, total - cap)
+        if count is None:
+            count = total - first
+        rec = np.zeros(max(count, 0), TRACE_DYN_RECORD)
+        dmaps = np.zeros((max(count, 0), dsnap), GAUSSIAN4D) if dsnap else None
+        _lib.check(_lib.lib().phd_trace_read_dynamic(self._h, int(first), int(count), _ptr(rec), _ptr(dmaps)),
+                   "phd_trace_read_dynamic")
+        return (rec, dmaps) if dsnap else rec
 
     def expected_pose(self):
         pose = np.zeros(1, POSE)

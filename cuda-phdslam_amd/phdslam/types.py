@@ -27,6 +27,10 @@ TRACE_RECORD = np.dtype([("step", np.uint64), ("n_live", np.int32), ("n_measure"
                          ("reserved", np.int32)])
 assert TRACE_RECORD.itemsize == 96
 TRACE_CARD_DIST = 1
+# phd_trace_dyn_record: the dynamic half of one scan of a mixed-model trace (feature_model 2)
+TRACE_DYN_RECORD = np.dtype([("card_expected", np.float32), ("card_map", np.float32), ("map_size", np.int32),
+                             ("reserved", np.int32, (5,))])
+assert TRACE_DYN_RECORD.itemsize == 32
 
 MOTION_CV = 0
 MOTION_ACKERMAN = 1
@@ -58,7 +62,13 @@ class TraceRecord(ctypes.Structure):
                 ("card_map", _f), ("map_size", _i), ("status_errors", _i), ("reserved", _i)]
 
 
+class TraceDynRecord(ctypes.Structure):
+    """phd_trace_dyn_record (include/phd_types.h), 32 bytes; TRACE_DYN_RECORD is the same layout for arrays."""
+    _fields_ = [("card_expected", _f), ("card_map", _f), ("map_size", _i), ("reserved", _i * 5)]
+
+
 assert ctypes.sizeof(TraceRecord) == TRACE_RECORD.itemsize
+assert ctypes.sizeof(TraceDynRecord) == TRACE_DYN_RECORD.itemsize == 32 and TraceDynRecord.map_size.offset == 8
 assert all(getattr(TraceRecord, k).offset == TRACE_RECORD.fields[k][1] for k in TRACE_RECORD.names)
 
 

@@ -390,8 +390,8 @@ int phd_expected_map_blocks(phd_ctx* ctx, const void* dev_blocks, int world, lon
  * combination Σ_n exp(w_n) cn_n[k] recoverSlamState makes, else the arg-max
  * particle's (zeros until a CPHD update has run).  capacity 0 turns the trace
  * off and frees the rings; enabling again restarts the count at 0.
- * PHD_E_UNSUPPORTED: feature_model 2, n_predict_particles > 1,
- * PHD_TRACE_CARD_DIST without CPHD; and from a traced phd_step on a context
+ * PHD_E_UNSUPPORTED: feature_model 2 (its trace: phd_trace_enable_mixed,
+ * below), n_predict_particles > 1, PHD_TRACE_CARD_DIST without CPHD; and from a traced phd_step on a context
  * that holds migrated (sharded) slabs.  Needs phd_set_config first.  Replay
  * mode is supported (every record is the same).  Synchronises (an allocation,
  * not a step). */
@@ -408,6 +408,39 @@ int phd_trace_read(phd_ctx* ctx, long first, int count, phd_trace_record* record
 /* The enabled trace: ring capacity (0: off), snapshot components per scan and
  * floats per cardinality row (0 without PHD_TRACE_CARD_DIST). */
 int phd_trace_shape(phd_ctx* ctx, int* capacity, int* map_snapshot_cap, int* card_k);
+
+/* ---- the trace of the mixed static + dynamic model (feature_model 2) ----
+ * phd_trace_enable_mixed turns on what phd_trace_enable turns on — the ring of
+ * phd_trace_record, whose cardinality and map fields describe the STATIC maps
+ * of a mixed context, and with map_snapshot_cap > 0 their snapshots — and a
+ * parallel ring of `capacity` phd_trace_dyn_record (phd_types.h) with the same
+ * scan index: the dynamic maps' card_expected (Σ_n exp(w_n) Σ_j w_nj, the
+ * static field's order and precision), and the arg-max particle's dynamic
+ * card_map and map_size; with dyn_snapshot_cap > 0 also capacity x
+ * dyn_snapshot_cap phd_gaussian4d: each scan's entry holds the first
+ * dyn_snapshot_cap components of that particle's posterior dynamic map in slab
+ * order (the row order of phd_export_dynamic_maps), zero past map_size.  Every
+ * traced phd_step appends both halves, from the store after the update and the
+ * normalisation and before the resample; on a scan without measurements from
+ * the predicted store.  phd_trace_count / phd_trace_read / phd_trace_shape
+ * serve the static half unchanged; capacity 0 (here or in phd_trace_enable)
+ * turns everything off and frees both rings.
+ * PHD_E_ARG: no phd_set_config, no phd_enable_dynamic.  PHD_E_UNSUPPORTED:
+ * feature_model other than 2 (phd_trace_enable in turn refuses feature_model
+ * 2), PHD_TRACE_CARD_DIST (the mixed model has no CPHD), n_predict_particles
+ * > 1; from a traced phd_step after feature_model or the dynamic capacity
+ * (phd_enable_dynamic) changed — enable the trace again; and from
+ * phd_trace_shard_pack / _append (the sharded step does not support
+ * feature_model 2).  Synchronises (an allocation, not a step). */
+int phd_trace_enable_mixed(phd_ctx* ctx, int capacity, int map_snapshot_cap, int dyn_snapshot_cap, unsigned flags);
+/* The dyn records [first, first + count) into records (count) and dmaps (count
+ * x dyn_snapshot_cap, may be NULL), by phd_trace_read's rules: one
+ * synchronisation, one copy per ring (two where the range wraps), PHD_E_ARG if
+ * part of the range has been overwritten or not written yet. */
+int phd_trace_read_dynamic(phd_ctx* ctx, long first, int count, phd_trace_dyn_record* records,
+                           phd_gaussian4d* dmaps);
+/* Dynamic snapshot components per scan of the enabled trace (0: none, or no mixed trace). */
+int phd_trace_shape_dynamic(phd_ctx* ctx, int* dyn_snapshot_cap);
 
 /* ---- the trace of a sharded step ----
  * With the trace on (phd_trace_enable on every rank's context, same arguments),

@@ -135,6 +135,17 @@ typedef struct phd_trace_record {
     int reserved;
 } phd_trace_record;
 
+/* The dynamic half of one scan of a mixed-model trace (feature_model 2,
+ * phd_trace_enable_mixed, phd_capi.h): a parallel ring with the capacity and
+ * the scan index of the phd_trace_record ring, whose cardinality and map
+ * fields describe the static maps on such a context. */
+typedef struct phd_trace_dyn_record {
+    float card_expected; /* Σ_n exp(w_n) Σ_j w_nj over the dynamic maps */
+    float card_map;      /* Σ_j w_j of the arg-max particle's dynamic map */
+    int map_size;        /* components of that dynamic map (true count) */
+    int reserved[5];     /* zero */
+} phd_trace_dyn_record;
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #define PHD_STATIC_ASSERT(c, m) static_assert(c, m)
@@ -163,5 +174,9 @@ PHD_STATIC_ASSERT(offsetof(phd_trace_record, map_pose) == 52, "map_pose@52");
 PHD_STATIC_ASSERT(offsetof(phd_trace_record, card_expected) == 76, "card_expected@76");
 PHD_STATIC_ASSERT(offsetof(phd_trace_record, map_size) == 84, "map_size@84");
 PHD_STATIC_ASSERT(offsetof(phd_trace_record, status_errors) == 88, "status_errors@88");
+PHD_STATIC_ASSERT(sizeof(phd_trace_dyn_record) == 32, "phd_trace_dyn_record must be 32 B");
+PHD_STATIC_ASSERT(offsetof(phd_trace_dyn_record, card_map) == 4, "dyn card_map@4");
+PHD_STATIC_ASSERT(offsetof(phd_trace_dyn_record, map_size) == 8, "dyn map_size@8");
+PHD_STATIC_ASSERT(offsetof(phd_trace_dyn_record, reserved) == 12, "dyn reserved@12");
 
 #endif /* PHD_TYPES_H */
