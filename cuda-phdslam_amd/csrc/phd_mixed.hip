@@ -27,7 +27,8 @@
  *        order; one lane sums them in that order in double, so the moments
  *        equal the oracle's bit for bit; static out-of-range components are
  *        appended.
- * The arithmetic is include/phd_mixed.h (shared with the oracle).  This is a
+ * The arithmetic is include/phd_mixed.h (the oracle restates it on its own in
+ * oracle/mixed_ref.h; both are held to tests/mixed_ref64.py).  This is a
  * correctness-first form: no benchmark config of the reference uses the mixed
  * model, so it is not tuned like the static update.
  */

@@ -2,12 +2,14 @@
  * phd_mixed.h — arithmetic of the mixed static + dynamic feature model
  * (feature_model = 2), host + device, header-only.
  *
- * Shared by the GPU kernels (csrc/phd_mixed.hip) and the CPU oracle
- * (oracle/scphd_cpu.cpp orc_update_mixed / orc_predict_dynamic): parity of the
- * mixed path checks the orchestration (classification, weights, normalisers,
- * prune, merge order); the expressions below are pinned by closed-form tests
- * (tests/test_oracle_closed_form.py: 4x4 inverse, Kalman update and the
- * constant-velocity prediction against float64 numpy).
+ * Used by the GPU kernels (csrc/phd_mixed.hip) only.  The CPU oracle
+ * (oracle/scphd_cpu.cpp orc_update_mixed / orc_predict_dynamic) restates the
+ * same reference routines on its own in oracle/mixed_ref.h; the two share
+ * nothing but the phd_detmath.h primitives (exp, log, atan2, sincos: D14, D16).
+ * Both are held to a float64 reference written from the model
+ * (tests/mixed_ref64.py: tests/test_mixed_ref64.py the oracle,
+ * tests/test_gpu_mixed_ref64.py the device), and to each other
+ * (tests/test_gpu_mixed.py).
  *
  * Every function restates one reference routine with its float / double
  * promotions (cited per function).  Device-side pow(x, 2) of the reference is

@@ -917,6 +917,22 @@ long orc_update_mixed(const phd_slam_config* cfgp, int n, const phd_pose* poses,
     s_off_out[0] = 0;
     d_off_out[0] = 0;
     g_near_counts.assign((size_t)n, 0);
+    if (M == 0) {
+        // an empty scan: the driver runs no update (main.cpp:1260), as phd_update does —
+        // both maps and the weights stay as they are
+        if (s_off_in[n] - s_off_in[0] > s_cap || d_off_in[n] - d_off_in[0] > d_cap) return -1;
+        for (int p = 0; p <= n; p++) {
+            s_off_out[p] = s_off_in[p] - s_off_in[0];
+            d_off_out[p] = d_off_in[p] - d_off_in[0];
+        }
+        std::copy(s_in + s_off_in[0], s_in + s_off_in[n], s_out);
+        std::copy(d_in + d_off_in[0], d_in + d_off_in[n], d_out);
+        for (int p = 0; p < n; p++) {
+            delta[p] = 0.0f;
+            if (margin) margin[p] = FLT_MAX;  // no decision was made
+        }
+        return 0;
+    }
     for (int p = 0; p < n; p++) {
         Margin mg;
         const phd_pose& pose = poses[p];

@@ -6,9 +6,11 @@ Tolerances as tests/test_gpu_parity.py: fp32 fields within 1e-5 relative;
 maps compared in order (both sides emit merged components in the greedy's
 selection order, then the static out-of-range components); particles whose
 oracle decided a prune / merge / range class within 1e-4 of its threshold may
-differ only in the components those decisions touch (compared as multisets);
-birth means use the platform cosf / sinf (≤ 1 ulp apart), everything else is
-shared arithmetic (include/phd_mixed.h).
+differ only in the components those decisions touch (compared as multisets).
+The two sides state the arithmetic separately (include/phd_mixed.h the device,
+oracle/mixed_ref.h the oracle) and share the phd_detmath.h primitives: exp /
+log (D14), atan2, and the births' phd_det_sincosf (D16).  What both could have
+wrong alike is held to a float64 reference in tests/test_gpu_mixed_ref64.py.
 """
 import numpy as np
 import pytest
@@ -125,7 +127,7 @@ def test_predict_dynamic_matches_oracle(gpu):
     o = pyoracle.predict_dynamic(cfg, pyoracle.predict_dynamic(cfg, dm))
     assert np.array_equal(go, dof)
     for fld in ("weight", "mean", "cov"):
-        assert np.array_equal(g[fld], o[fld]), fld  # shared arithmetic: bit for bit
+        assert np.array_equal(g[fld], o[fld]), fld  # the same expressions on both sides: bit for bit
 
 
 def test_mixed_sequence_with_resample(gpu):
