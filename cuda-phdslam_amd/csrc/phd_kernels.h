@@ -1,6 +1,6 @@
 /*
  * phd_kernels.h — kernel argument structs, LDS layout and launch declarations
- * shared by phd_kernels.hip and phd_capi.hip.
+ * shared by phd_kernels.hip and the host units (phd_capi_*.hip).
  */
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1533,7 +1533,7 @@ __device__ __forceinline__ void update_body(const UpdateArgs& a) {
     // [1..3] CPHD Σw in range, Σ(1-pd)w, Σw; [4] (float) CPHD non-detection factor
     double* s_uni = (double*)(smem + L.uni);
     // the launch's last a.prio workgroups at the highest wave priority
-    // (prio_tail in phd_capi.hip): they finish the launch, and their
+    // (prio_tail in phd_capi_update.hip): they finish the launch, and their
     // instructions issue ahead of the earlier workgroups' on a shared SIMD
     if (b_ >= grid_ - a.prio) __builtin_amdgcn_s_setprio(3);
     // three-launch CPHD: this particle's handoff (part A writes it, part C reads it)

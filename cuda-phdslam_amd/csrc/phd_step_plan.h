@@ -1,5 +1,5 @@
 /* phd_step_plan.h — which resample form a phd_step takes, decided once from
- * plain values before anything is enqueued (phd_capi.hip follows the plan).
+ * plain values before anything is enqueued (phd_capi_step.hip follows the plan).
  * Host C++17, no HIP: tests/step_plan_harness.cpp builds it by itself. */
 #pragma once
 
@@ -9,7 +9,7 @@
 
 namespace phd {
 
-/* entries per workgroup of the chunked resample (phd_capi.hip asserts it RS_THREADS) */
+/* entries per workgroup of the chunked resample (phd_capi_step.hip asserts it RS_THREADS) */
 constexpr int kRsChunk = 1024;
 
 struct StepFacts {

@@ -1,6 +1,6 @@
 /*
  * phd_trace.h — launch interface of the per-scan estimate trace (phd_trace.hip),
- * called by phd_step (phd_capi.hip) between the update and the resample, and
+ * called by phd_step (phd_capi_step.hip) between the update and the resample, and
  * of its sharded form, called by phd_trace_shard_pack / phd_trace_shard_append.
  */
 #pragma once

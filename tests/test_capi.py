@@ -157,12 +157,21 @@ def test_synth_scenario_deterministic(built):
     np.testing.assert_allclose(lw, -np.log(8), rtol=1e-6)
 
 
+HOST_UNITS = ["phd_capi_ctx.hip", "phd_capi_update.hip", "phd_capi_step.hip", "phd_capi_shard.hip",
+              "phd_capi_trace.hip", "phd_capi_estimate.hip"]
+
+
 @pytest.mark.parametrize("src,defines", [
     ("phd_kernels.hip", ["-DPHD_STAMPS"]),
     ("phd_kernels.hip", ["-DPHD_XK=3"]),
     ("phd_kernels.hip", ["-DPHD_XK=10", "-DPHD_STAMPS"]),
-    ("phd_capi.hip", ["-DPHD_STAMPS", "-DPHD_STAMP_PART_A"]),
+    # the host units that read PHD_STAMPS / PHD_STAMP_PART_A (the update and the step) or take phd_debug_stamps (ctx)
+    ("phd_capi_update.hip", ["-DPHD_STAMPS", "-DPHD_STAMP_PART_A"]),
     ("phd_eap.hip", ["-DPHD_EAP_DEBUG"]),
+    ("phd_capi_step.hip", ["-DPHD_STAMPS", "-DPHD_STAMP_PART_A"]),
+    ("phd_capi_ctx.hip", ["-DPHD_STAMPS", "-DPHD_STAMP_PART_A"]),
+    # the timing-events knob sits in the update unit, apart from the other host units
+    *[(u, ["-DPHD_TIMING_EVENTS=0"]) for u in HOST_UNITS],
 ])
 def test_diagnostic_builds_compile(src, defines):
     """The diagnostic variants (stamps, ablations, EAP round timing: compile-time

@@ -224,7 +224,7 @@ def test_step_second_stream(gpu, case):
     """The same steps with the small capacities: part C's LDS (a few KB) cannot
     hold rs_step_block's 8.4 KB of tables, so the armed resample is launched as
     k_rs_step on the second stream beside part C.  (Before the LDS check in
-    phd_capi.hip the lead workgroup ran here all the same, read zeros past its
+    phd_capi_update.hip the lead workgroup ran here all the same, read zeros past its
     allocation and left the log-weights unnormalised: entry 0 of
     `split-4097-two_far` -208.017 against normalize()'s -199.974.)"""
     _step(case, "beside")
