@@ -320,10 +320,14 @@ int phd_enable_dynamic(phd_ctx* ctx, int dyn_capacity) {
         ctx->mx.d_cand.alloc(ns * mixed_cand_floats(ctx->cap.candidate_capacity)))
         return PHD_E_HIP;
     HIPCHK(mixed_set_lds_limit());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
     ctx->mx.on = true;
     ctx->mx.dcap = dyn_capacity;
     ctx->mx.dcur = 0;
+    // a context that holds migrated slabs: its references with bit 30 name the
+    // dynamic set X as well — resized with the rest (empty, like the new sets),
+    // so none of them is left stale
+    if (ctx->st.d_map_x && ensure_dyn_x(ctx)) return PHD_E_HIP;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return PHD_OK;
 }
 
@@ -358,6 +362,31 @@ int phd_load_dynamic_maps(phd_ctx* ctx, int n, const phd_gaussian4d* maps, const
                           ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->mx.d_dsize[ctx->mx.dcur], sizes.data(), n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->mx.x_live = false;  // (every reference is the identity, checked above: none names set X)
+    return PHD_OK;
+}
+
+/* Host image of the dynamic migration set X (sizes, and the maps when asked
+ * for); both stay empty before the first receive.  The copies are enqueued:
+ * the caller synchronises. */
+static int fetch_dyn_x(phd_ctx* ctx, std::vector<int>& size_x, std::vector<float>* map_x) {
+    if (!ctx->mx.d_dsize_x) return PHD_OK;
+    const size_t nx = ctx->mx.d_dsize_x.bytes() / sizeof(int);
+    size_x.resize(nx);
+    HIPCHK(hipMemcpyAsync(size_x.data(), ctx->mx.d_dsize_x, nx * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (map_x) {
+        map_x->resize(nx * PHD_DYN_FIELDS * ctx->mx.dcap);
+        HIPCHK(hipMemcpyAsync(map_x->data(), ctx->mx.d_dmap_x, map_x->size() * sizeof(float), hipMemcpyDeviceToHost,
+                              ctx->stream));
+    }
+    return PHD_OK;
+}
+
+/* every reference that names set X names a slab the dynamic set X has */
+static int check_dyn_refs(const phd_ctx* ctx, const std::vector<int>& src, const std::vector<int>& size_x) {
+    for (int r : src)
+        if (slab_in_x(r) && (size_t)slab_index(r) >= size_x.size())
+            return fail(PHD_E_ARG, "a slab reference names a slab the dynamic migration set X does not have");
     return PHD_OK;
 }
 
@@ -366,12 +395,14 @@ int phd_dynamic_sizes(phd_ctx* ctx, int* sizes) {
     if (!ctx->mx.on) return fail(PHD_E_ARG, "phd_enable_dynamic not called");
     if (set_device(ctx)) return PHD_E_HIP;
     const int n = ctx->n;
-    std::vector<int> src(n), dsz(ctx->nmax);
+    std::vector<int> src(n), dsz(ctx->nmax), dszx;
     HIPCHK(hipMemcpyAsync(src.data(), ctx->st.d_src, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(dsz.data(), ctx->mx.d_dsize[ctx->mx.dcur], ctx->nmax * sizeof(int), hipMemcpyDeviceToHost,
                           ctx->stream));
+    if (int rc = fetch_dyn_x(ctx, dszx, nullptr)) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int p = 0; p < n; p++) sizes[p] = dsz[slab_index(src[p])];
+    if (int rc = check_dyn_refs(ctx, src, dszx)) return rc;
+    for (int p = 0; p < n; p++) sizes[p] = slab_size(src[p], dsz.data(), dszx.data());
     return PHD_OK;
 }
 
@@ -381,19 +412,21 @@ int phd_export_dynamic_maps(phd_ctx* ctx, int n, const int* offsets, phd_gaussia
     if (!ctx->mx.on) return fail(PHD_E_ARG, "phd_enable_dynamic not called");
     if (set_device(ctx)) return PHD_E_HIP;
     const int dcap = ctx->mx.dcap;
-    std::vector<int> src(n), dsz(ctx->nmax);
-    std::vector<float> all((size_t)ctx->nmax * PHD_DYN_FIELDS * dcap);
+    std::vector<int> src(n), dsz(ctx->nmax), dszx;
+    std::vector<float> all((size_t)ctx->nmax * PHD_DYN_FIELDS * dcap), allx;
     HIPCHK(hipMemcpyAsync(src.data(), ctx->st.d_src, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(dsz.data(), ctx->mx.d_dsize[ctx->mx.dcur], ctx->nmax * sizeof(int), hipMemcpyDeviceToHost,
                           ctx->stream));
     HIPCHK(hipMemcpyAsync(all.data(), ctx->mx.d_dmap[ctx->mx.dcur], all.size() * sizeof(float), hipMemcpyDeviceToHost,
                           ctx->stream));
+    if (int rc = fetch_dyn_x(ctx, dszx, &allx)) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (int rc = check_dyn_refs(ctx, src, dszx)) return rc;
     for (int p = 0; p < n; p++) {
-        const int r = slab_index(src[p]);
         const int sz = offsets[p + 1] - offsets[p];
-        if (sz != dsz[r]) return fail(PHD_E_ARG, "offsets do not match the current dynamic map sizes");
-        const float* sl = all.data() + (size_t)r * PHD_DYN_FIELDS * dcap;
+        if (sz != slab_size(src[p], dsz.data(), dszx.data()))
+            return fail(PHD_E_ARG, "offsets do not match the current dynamic map sizes");
+        const float* sl = dyn_slab_map(src[p], (const float*)all.data(), (const float*)allx.data(), dcap);
         for (int k = 0; k < sz; k++) {
             phd_gaussian4d& g = maps[offsets[p] + k];
             g.weight = sl[k];

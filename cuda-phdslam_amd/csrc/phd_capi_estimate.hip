@@ -86,7 +86,8 @@ int phd_expected_map_dynamic(phd_ctx* ctx, phd_gaussian4d* out, long out_cap, lo
     if (set_device(ctx)) return PHD_E_HIP;
     std::string err;
     const long nout = mixed_expected_map_dynamic(ctx->stream, ctx->st.d_src, ctx->mx.d_dmap[ctx->mx.dcur],
-                                                 ctx->mx.d_dsize[ctx->mx.dcur], ctx->n, ctx->mx.dcap, ctx->st.d_logw,
+                                                 ctx->mx.d_dsize[ctx->mx.dcur], ctx->mx.d_dmap_x, ctx->mx.d_dsize_x,
+                                                 ctx->n, ctx->mx.dcap, ctx->st.d_logw,
                                                  ctx->cfg.minSeparation, out, out ? out_cap : 0, err);
     if (nout < 0) return fail(PHD_E_HIP, "dynamic expected map: " + err);
     *n_out = nout;

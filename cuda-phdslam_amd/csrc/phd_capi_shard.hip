@@ -23,7 +23,63 @@ static int ensure_x(phd_ctx* c) {
         HIPCHK(hipMemsetAsync(c->st.d_size_x, 0, c->n * sizeof(int), c->stream));
     }
     if (rec_cn_stride(c) && c->cn.d_x.ensure((size_t)c->n * c->cn.stride)) return PHD_E_HIP;
+    if (rec_dcap(c)) {  // mixed: the dynamic twin; from here on references may name it
+        if (ensure_dyn_x(c)) return PHD_E_HIP;
+        c->mx.x_live = true;
+    }
     return ensure_cn(c);
+}
+
+int ensure_dyn_x(phd_ctx* c) {
+    if (c->mx.d_dmap_x) return PHD_OK;
+    if (c->mx.d_dmap_x.alloc((size_t)c->n * PHD_DYN_FIELDS * c->mx.dcap) || c->mx.d_dsize_x.alloc(c->n)) return PHD_E_HIP;
+    HIPCHK(hipMemsetAsync(c->mx.d_dsize_x, 0, c->n * sizeof(int), c->stream));
+    return PHD_OK;
+}
+
+/* The record kernels of a mixed context (phd_mixed.hip) see the store through
+ * this; the static kernels' arguments otherwise. */
+static MixedStore mixed_store(const phd_ctx* c) {
+    MixedStore S;
+    S.cap = c->cap.map_capacity;
+    S.dcap = c->mx.dcap;
+    S.src = c->st.d_src;
+    S.map_in = c->st.d_map[c->st.cur];
+    S.size_in = c->st.d_size[c->st.cur];
+    S.map_x = c->st.d_map_x;
+    S.size_x = c->st.d_size_x;
+    S.dmap_in = c->mx.d_dmap[c->mx.dcur];
+    S.dsize_in = c->mx.d_dsize[c->mx.dcur];
+    S.dmap_x = c->mx.d_dmap_x;
+    S.dsize_x = c->mx.d_dsize_x;
+    S.pose = c->st.d_pose;
+    S.logw = c->st.d_logw;
+    return S;
+}
+
+/* What is refused of a sharded resample, whatever its form.  The mixed model
+ * (feature_model 2, PHD) takes part once phd_enable_dynamic was called. */
+static int shard_supported(const phd_ctx* ctx) {
+    if (ctx->cfg.nPredictParticles > 1 || ctx->n != ctx->n_base)
+        return fail(PHD_E_UNSUPPORTED, "sharded resample with n_predict_particles > 1 (shards hold n_particles each)");
+    if (ctx->cfg.featureModel == PHD_FEATURE_MIXED) {
+        if (ctx->cfg.filterType != PHD_FILTER_PHD) return fail(PHD_E_UNSUPPORTED, "feature_model 2 with the CPHD filter");
+        if (!ctx->mx.on) return fail(PHD_E_ARG, "feature_model 2 needs phd_enable_dynamic");
+    } else if (ctx->cfg.featureModel != PHD_FEATURE_STATIC) {
+        return fail(PHD_E_UNSUPPORTED, "sharded resample with feature_model != 0");
+    }
+    return PHD_OK;
+}
+
+/* The caller sized its record buffers by phd_record_bytes: a mixed record of
+ * another dynamic capacity than it last returned would not fit them. */
+static int record_size_known(const phd_ctx* ctx) {
+    if (rec_dcap(ctx) && rec_dcap(ctx) != ctx->sh.rec_dcap)
+        return fail(PHD_E_ARG, "the record size changed (feature_model 2: dynamic capacity " +
+                                   std::to_string(rec_dcap(ctx)) + ", phd_record_bytes last reported " +
+                                   std::to_string(ctx->sh.rec_dcap) +
+                                   "): call phd_enable_dynamic first, then size the record buffers by phd_record_bytes");
+    return PHD_OK;
 }
 
 extern "C" {
@@ -51,10 +107,7 @@ int phd_global_resample(phd_ctx* ctx, float* dev_w_all, int n_total, int offset,
                         int* dev_parents, float* neff, int* resampled) {
     if (!ctx || !dev_w_all || !dev_parents || n_total < ctx->n || offset < 0 || offset + ctx->n > n_total)
         return fail(PHD_E_ARG, "bad arguments to phd_global_resample");
-    if (ctx->cfg.nPredictParticles > 1 || ctx->n != ctx->n_base)
-        return fail(PHD_E_UNSUPPORTED, "sharded resample with n_predict_particles > 1 (shards hold n_particles each)");
-    if (ctx->cfg.featureModel != PHD_FEATURE_STATIC)
-        return fail(PHD_E_UNSUPPORTED, "sharded resample with feature_model != 0");
+    if (int rc0 = shard_supported(ctx)) return rc0;
     if (set_device(ctx)) return PHD_E_HIP;
     if (ctx->rs.d_cdf_g.ensure(n_total)) return PHD_E_HIP;
     float* out = ctx->d_out + 40;
@@ -186,10 +239,9 @@ int phd_shard_resample(phd_ctx* ctx, float* dev_w_all, int world, int rank, uint
         !send_records || !recv_records || world < 1 || world > 1024 || rank < 0 || rank >= world ||
         (long long)world * ctx->n > (long long)RS_MAX_CHUNKS * RS_THREADS || send_capacity < 0 || (send_capacity > 0 && !dev_send_records))
         return fail(PHD_E_ARG, "bad arguments to phd_shard_resample");
-    if (ctx->cfg.nPredictParticles > 1 || ctx->n != ctx->n_base)
-        return fail(PHD_E_UNSUPPORTED, "sharded resample with n_predict_particles > 1 (shards hold n_particles each)");
-    if (ctx->cfg.featureModel != PHD_FEATURE_STATIC)
-        return fail(PHD_E_UNSUPPORTED, "sharded resample with feature_model != 0");
+    if (int rc0 = shard_supported(ctx)) return rc0;
+    if (send_capacity > 0)
+        if (int rc0 = record_size_known(ctx)) return rc0;
     if (set_device(ctx)) return PHD_E_HIP;
     const int n_total = world * ctx->n;
     if (ensure_mig(ctx, world)) return PHD_E_HIP;
@@ -201,11 +253,16 @@ int phd_shard_resample(phd_ctx* ctx, float* dev_w_all, int world, int rank, uint
         if (ensure_cn(ctx)) return PHD_E_HIP;
         // records this rank sends (count on the device) from the pre-resample
         // store; they carry the new log-weight
-        hipLaunchKernelGGL(k_pack, dim3(std::min(send_capacity, 256)), dim3(256), 0, ctx->stream,
-                           (const int*)(ctx->sh.d_mig + 3 * world), (const int*)dev_send_src, send_capacity,
-                           ctx->cap.map_capacity, ctx->st.d_src, ctx->st.d_map[ctx->st.cur], ctx->st.d_size[ctx->st.cur],
-                           ctx->st.d_map_x, ctx->st.d_size_x, ctx->st.d_pose, ctx->st.d_logw, 1, new_log_weight,
-                           ctx->cn.d_coef, ctx->cn.d_x, rec_cn_stride(ctx), (float*)dev_send_records);
+        if (rec_dcap(ctx))
+            HIPCHK(mixed_launch_pack(mixed_store(ctx), std::min(send_capacity, 256), (const int*)(ctx->sh.d_mig + 3 * world),
+                                     (const int*)dev_send_src, send_capacity, 1, new_log_weight,
+                                     (float*)dev_send_records, ctx->stream));
+        else
+            hipLaunchKernelGGL(k_pack, dim3(std::min(send_capacity, 256)), dim3(256), 0, ctx->stream,
+                               (const int*)(ctx->sh.d_mig + 3 * world), (const int*)dev_send_src, send_capacity,
+                               ctx->cap.map_capacity, ctx->st.d_src, ctx->st.d_map[ctx->st.cur], ctx->st.d_size[ctx->st.cur],
+                               ctx->st.d_map_x, ctx->st.d_size_x, ctx->st.d_pose, ctx->st.d_logw, 1, new_log_weight,
+                               ctx->cn.d_coef, ctx->cn.d_x, rec_cn_stride(ctx), (float*)dev_send_records);
         HIPCHK(hipGetLastError());
     }
     int* h = ctx->sh.h_mig;  // (written by the plan's tail)
@@ -241,10 +298,8 @@ int phd_shard_resample_async(phd_ctx* ctx, float* dev_w_all, int world, int rank
         (world > 1 && block_records > 0 && !dev_send_blocks) || (overflow_capacity > 0 && !dev_overflow))
         return fail(PHD_E_ARG, "bad arguments to phd_shard_resample_async");
     if (ctx->sh.open) return fail(PHD_E_ARG, "phd_shard_poll the previous plan first");
-    if (ctx->cfg.nPredictParticles > 1 || ctx->n != ctx->n_base)
-        return fail(PHD_E_UNSUPPORTED, "sharded resample with n_predict_particles > 1 (shards hold n_particles each)");
-    if (ctx->cfg.featureModel != PHD_FEATURE_STATIC)
-        return fail(PHD_E_UNSUPPORTED, "sharded resample with feature_model != 0");
+    if (int rc0 = shard_supported(ctx)) return rc0;
+    if (int rc0 = record_size_known(ctx)) return rc0;  // (before anything is enqueued: nothing is written)
     if (set_device(ctx)) return PHD_E_HIP;
     if (ensure_mig(ctx, world)) return PHD_E_HIP;
     if (ensure_cn(ctx)) return PHD_E_HIP;
@@ -284,7 +339,12 @@ int phd_shard_resample_async(phd_ctx* ctx, float* dev_w_all, int world, int rank
                                dev_send_src, dev_recv_rec, new_log_weight, block_records);
         if (rc) return rc;
     }
-    if (world > 1) {  // records from the pre-resample store (the pointers are swapped below)
+    if (world > 1 && rec_dcap(ctx)) {  // (mixed: the records carry the dynamic maps, phd_mixed.hip)
+        HIPCHK(mixed_launch_pack_blocks(mixed_store(ctx), std::min(ctx->n, 256), (const int*)ctx->sh.d_mig, world,
+                                        (const int*)dev_send_src, block_records, overflow_capacity, new_log_weight,
+                                        (float*)dev_send_blocks, (float*)dev_overflow,
+                                        ctx->sh.h_mig_dev + 3 * world + MIG_OVF_CAP, ctx->stream));
+    } else if (world > 1) {  // records from the pre-resample store (the pointers are swapped below)
         hipLaunchKernelGGL(k_pack_blocks, dim3(std::min(ctx->n, 256)), dim3(256), 0, ctx->stream,
                            (const int*)ctx->sh.d_mig, world, (const int*)dev_send_src, block_records, overflow_capacity,
                            ctx->cap.map_capacity, (const int*)ctx->st.d_src, (const float*)ctx->st.d_map[ctx->st.cur],
@@ -336,12 +396,18 @@ int phd_shard_receive_blocks(phd_ctx* ctx, const void* dev_recv_blocks, int bloc
     if (!ctx || !dev_recv_rec || block_records < 0 || (block_records > 0 && !dev_recv_blocks) || !ctx->sh.world)
         return fail(PHD_E_ARG, "bad arguments to phd_shard_receive_blocks");
     if (set_device(ctx)) return PHD_E_HIP;
+    if (int rc0 = record_size_known(ctx)) return rc0;
     if (ensure_x(ctx)) return PHD_E_HIP;
     ctx->st.src_fresh = false;
-    hipLaunchKernelGGL(k_unpack_blocks, dim3(std::min(ctx->n, 256)), dim3(256), 0, ctx->stream, (const float*)dev_recv_blocks,
-                       (const float*)nullptr, block_records, 0, (const int*)ctx->sh.d_mig, ctx->sh.world,
-                       ctx->sh.rank, dev_recv_rec, ctx->n, ctx->cap.map_capacity, ctx->st.d_map_x,
-                       ctx->st.d_size_x, ctx->st.d_src, ctx->st.d_pose, ctx->st.d_logw, ctx->cn.d_x, rec_cn_stride(ctx));
+    if (rec_dcap(ctx))
+        HIPCHK(mixed_launch_unpack_blocks(mixed_store(ctx), std::min(ctx->n, 256), (const float*)dev_recv_blocks,
+                                          (const float*)nullptr, block_records, 0, (const int*)ctx->sh.d_mig,
+                                          ctx->sh.world, ctx->sh.rank, dev_recv_rec, ctx->n, ctx->stream));
+    else
+        hipLaunchKernelGGL(k_unpack_blocks, dim3(std::min(ctx->n, 256)), dim3(256), 0, ctx->stream, (const float*)dev_recv_blocks,
+                           (const float*)nullptr, block_records, 0, (const int*)ctx->sh.d_mig, ctx->sh.world,
+                           ctx->sh.rank, dev_recv_rec, ctx->n, ctx->cap.map_capacity, ctx->st.d_map_x,
+                           ctx->st.d_size_x, ctx->st.d_src, ctx->st.d_pose, ctx->st.d_logw, ctx->cn.d_x, rec_cn_stride(ctx));
     HIPCHK(hipGetLastError());
     return PHD_OK;
 }
@@ -392,11 +458,19 @@ int phd_shard_receive_overflow(phd_ctx* ctx, const void* dev_recv_overflow, int 
     if (ctx->sh.pend_count == 0) return PHD_OK;
     if (!dev_recv_overflow) return fail(PHD_E_ARG, "phd_shard_receive_overflow: pending slots need the records");
     if (set_device(ctx)) return PHD_E_HIP;
+    if (int rc0 = record_size_known(ctx)) return rc0;
     ctx->st.src_fresh = false;
-    hipLaunchKernelGGL(k_unpack_blocks, dim3(std::min(ctx->n, 256)), dim3(256), 0, ctx->stream, (const float*)nullptr,
-                       (const float*)dev_recv_overflow, block_records, 1, (const int*)ctx->sh.d_mig, ctx->sh.world,
-                       ctx->sh.rank, dev_recv_rec, ctx->n, ctx->cap.map_capacity, ctx->st.d_map_x,
-                       ctx->st.d_size_x, ctx->st.d_src, ctx->st.d_pose, ctx->st.d_logw, ctx->cn.d_x, rec_cn_stride(ctx));
+    if (rec_dcap(ctx)) {
+        if (ensure_x(ctx)) return PHD_E_HIP;  // (the sets X exist since the blocks' receive; marks them live again)
+        HIPCHK(mixed_launch_unpack_blocks(mixed_store(ctx), std::min(ctx->n, 256), (const float*)nullptr,
+                                          (const float*)dev_recv_overflow, block_records, 1, (const int*)ctx->sh.d_mig,
+                                          ctx->sh.world, ctx->sh.rank, dev_recv_rec, ctx->n, ctx->stream));
+    } else {
+        hipLaunchKernelGGL(k_unpack_blocks, dim3(std::min(ctx->n, 256)), dim3(256), 0, ctx->stream, (const float*)nullptr,
+                           (const float*)dev_recv_overflow, block_records, 1, (const int*)ctx->sh.d_mig, ctx->sh.world,
+                           ctx->sh.rank, dev_recv_rec, ctx->n, ctx->cap.map_capacity, ctx->st.d_map_x,
+                           ctx->st.d_size_x, ctx->st.d_src, ctx->st.d_pose, ctx->st.d_logw, ctx->cn.d_x, rec_cn_stride(ctx));
+    }
     HIPCHK(hipGetLastError());
     return PHD_OK;
 }
@@ -412,7 +486,9 @@ int phd_update_pending(phd_ctx* ctx, const phd_ackerman_control* u, int do_predi
         HIPCHK(hipMemcpyAsync(dev_logw_out, ctx->st.d_logw, ctx->n * sizeof(float), hipMemcpyDeviceToDevice,
                               ctx->stream));
     if (ctx->sh.ev_logw) HIPCHK(hipEventRecord(ctx->sh.ev_logw, ctx->stream));  // (the mirror is complete here)
-    ctx->st.src_fresh = true;  // the pending slots (the only references off the identity) were re-updated
+    // the pending slots (the only references off the identity) were re-updated;
+    // (mixed: its update does not keep this flag, the plan always reads the references)
+    if (ctx->cfg.featureModel == PHD_FEATURE_STATIC) ctx->st.src_fresh = true;
     return PHD_OK;
 }
 
@@ -422,10 +498,15 @@ int phd_shard_receive(phd_ctx* ctx, const void* dev_records, const int* dev_recv
         return fail(PHD_E_ARG, "bad arguments to phd_shard_receive");
     if (n_slots == 0) return PHD_OK;
     if (set_device(ctx)) return PHD_E_HIP;
+    if (int rc0 = record_size_known(ctx)) return rc0;
     if (ensure_x(ctx)) return PHD_E_HIP;
-    hipLaunchKernelGGL(k_unpack_slots, dim3(n_slots), dim3(256), 0, ctx->stream, (const float*)dev_records,
-                       dev_recv_rec, n_slots, first_slot, ctx->cap.map_capacity, ctx->st.d_map_x, ctx->st.d_size_x,
-                       ctx->st.d_src, ctx->st.d_pose, ctx->st.d_logw, ctx->cn.d_x, rec_cn_stride(ctx));
+    if (rec_dcap(ctx))
+        HIPCHK(mixed_launch_unpack_slots(mixed_store(ctx), (const float*)dev_records, dev_recv_rec, n_slots, first_slot,
+                                         ctx->stream));
+    else
+        hipLaunchKernelGGL(k_unpack_slots, dim3(n_slots), dim3(256), 0, ctx->stream, (const float*)dev_records,
+                           dev_recv_rec, n_slots, first_slot, ctx->cap.map_capacity, ctx->st.d_map_x, ctx->st.d_size_x,
+                           ctx->st.d_src, ctx->st.d_pose, ctx->st.d_logw, ctx->cn.d_x, rec_cn_stride(ctx));
     HIPCHK(hipGetLastError());
     return PHD_OK;
 }
@@ -446,7 +527,17 @@ int phd_set_log_weights(phd_ctx* ctx, const float* dev_src) {
 
 int phd_record_bytes(const phd_ctx* ctx, size_t* bytes) {
     if (!ctx || !bytes) return fail(PHD_E_ARG, "null argument");
-    *bytes = record_words(ctx->cap.map_capacity, rec_cn_stride(ctx)) * sizeof(float);
+    const int dcap = rec_dcap(ctx);
+    *bytes = record_words_mixed(ctx->cap.map_capacity, rec_cn_stride(ctx), dcap) * sizeof(float);
+    // what the caller now sizes its buffers for (record_size_known); not part of the filter's state
+    const_cast<phd_ctx*>(ctx)->sh.rec_dcap = dcap;
+    return PHD_OK;
+}
+
+int phd_record_layout_bytes(int map_capacity, int cn_stride, int dyn_capacity, size_t* bytes) {
+    if (map_capacity < 0 || cn_stride < 0 || dyn_capacity < 0 || !bytes)
+        return fail(PHD_E_ARG, "bad arguments to phd_record_layout_bytes");
+    *bytes = record_words_mixed(map_capacity, cn_stride, dyn_capacity) * sizeof(float);
     return PHD_OK;
 }
 
@@ -454,11 +545,16 @@ int phd_pack_particles(phd_ctx* ctx, const int* dev_src_idx, int count, void* de
     if (!ctx || (count > 0 && (!dev_src_idx || !dev_records))) return fail(PHD_E_ARG, "bad arguments");
     if (count <= 0) return PHD_OK;
     if (set_device(ctx)) return PHD_E_HIP;
+    if (int rc0 = record_size_known(ctx)) return rc0;
     if (ensure_cn(ctx)) return PHD_E_HIP;
-    hipLaunchKernelGGL(k_pack, dim3(count), dim3(256), 0, ctx->stream, (const int*)nullptr, dev_src_idx, count,
-                       ctx->cap.map_capacity, ctx->st.d_src, ctx->st.d_map[ctx->st.cur], ctx->st.d_size[ctx->st.cur], ctx->st.d_map_x,
-                       ctx->st.d_size_x, ctx->st.d_pose, ctx->st.d_logw, 0, 0.f, ctx->cn.d_coef, ctx->cn.d_x,
-                       rec_cn_stride(ctx), (float*)dev_records);
+    if (rec_dcap(ctx))
+        HIPCHK(mixed_launch_pack(mixed_store(ctx), count, (const int*)nullptr, dev_src_idx, count, 0, 0.f,
+                                 (float*)dev_records, ctx->stream));
+    else
+        hipLaunchKernelGGL(k_pack, dim3(count), dim3(256), 0, ctx->stream, (const int*)nullptr, dev_src_idx, count,
+                           ctx->cap.map_capacity, ctx->st.d_src, ctx->st.d_map[ctx->st.cur], ctx->st.d_size[ctx->st.cur], ctx->st.d_map_x,
+                           ctx->st.d_size_x, ctx->st.d_pose, ctx->st.d_logw, 0, 0.f, ctx->cn.d_coef, ctx->cn.d_x,
+                           rec_cn_stride(ctx), (float*)dev_records);
     HIPCHK(hipGetLastError());
     return PHD_OK;
 }
@@ -468,10 +564,14 @@ int phd_unpack_particles(phd_ctx* ctx, const void* dev_records, const int* dev_d
     if (count <= 0) return PHD_OK;
     if (count > ctx->n) return fail(PHD_E_ARG, "more migrants than particles");
     if (set_device(ctx)) return PHD_E_HIP;
+    if (int rc0 = record_size_known(ctx)) return rc0;
     if (ensure_x(ctx)) return PHD_E_HIP;
-    hipLaunchKernelGGL(k_unpack, dim3(count), dim3(256), 0, ctx->stream, (const float*)dev_records, dev_dst_idx,
-                       (const int*)nullptr, count, ctx->cap.map_capacity, ctx->st.d_map_x, ctx->st.d_size_x, ctx->st.d_src,
-                       ctx->st.d_pose, ctx->st.d_logw, ctx->cn.d_x, rec_cn_stride(ctx));
+    if (rec_dcap(ctx))
+        HIPCHK(mixed_launch_unpack(mixed_store(ctx), (const float*)dev_records, dev_dst_idx, count, ctx->stream));
+    else
+        hipLaunchKernelGGL(k_unpack, dim3(count), dim3(256), 0, ctx->stream, (const float*)dev_records, dev_dst_idx,
+                           (const int*)nullptr, count, ctx->cap.map_capacity, ctx->st.d_map_x, ctx->st.d_size_x, ctx->st.d_src,
+                           ctx->st.d_pose, ctx->st.d_logw, ctx->cn.d_x, rec_cn_stride(ctx));
     HIPCHK(hipGetLastError());
     return PHD_OK;
 }

@@ -176,12 +176,28 @@ int rs_mode(const phd_ctx* ctx) {
     return ctx->z.M > 0 ? 1 : 0;
 }
 
-/* predictMapMixed (one phdPredict): every slab of the dynamic set, in -> out. */
-static int launch_predict_dynamic(phd_ctx* ctx) {
+/* predictMapMixed (one phdPredict).  All particles: every slab of the dynamic
+ * set, in -> out by slab id, and — while references may name it — every slab
+ * of the dynamic set X in place; a slab that several particles share (copy on
+ * write after a resample, several slots of one record) is a slab still, so it
+ * advances once.  Slots (a sharded step's pending slots, whose records came
+ * after this step's predict was enqueued): the slabs of set X they name, once
+ * each (mixed_launch_predict_x); the current set stays where it is. */
+static int launch_predict_dynamic(phd_ctx* ctx, const int* slots = nullptr, int count = 0) {
     if (!ctx->mx.on) return fail(PHD_E_ARG, "feature_model 2 needs phd_enable_dynamic");
+    const phd_mx_cfg mc = phd_mx_config(&ctx->cfg);
+    if (slots) {
+        if (ctx->mx.d_dmap_x)
+            HIPCHK(mixed_launch_predict_x(slots, count, ctx->st.d_src, ctx->mx.dcap, ctx->mx.d_dmap_x, ctx->mx.d_dsize_x,
+                                          mc, ctx->stream));
+        return PHD_OK;
+    }
     const int din = ctx->mx.dcur, dout = din ^ 1;
     HIPCHK(mixed_launch_predict(ctx->nmax, ctx->mx.dcap, ctx->mx.d_dmap[din], ctx->mx.d_dsize[din], ctx->mx.d_dmap[dout],
-                                ctx->mx.d_dsize[dout], phd_mx_config(&ctx->cfg), ctx->stream));
+                                ctx->mx.d_dsize[dout], mc, ctx->stream));
+    if (ctx->mx.x_live)
+        HIPCHK(mixed_launch_predict_x(nullptr, (int)(ctx->mx.d_dsize_x.bytes() / sizeof(int)), nullptr, ctx->mx.dcap,
+                                      ctx->mx.d_dmap_x, ctx->mx.d_dsize_x, mc, ctx->stream));
     ctx->mx.dcur = dout;
     return PHD_OK;
 }
@@ -191,8 +207,7 @@ static int launch_predict(phd_ctx* ctx, phd_ackerman_control u, const void* nois
                           const int* slots, int count) {
     if (count <= 0) return PHD_OK;
     if (ctx->cfg.featureModel == PHD_FEATURE_MIXED) {  // predictMapMixed with every phdPredict (phdfilter.cu:1241-1242)
-        if (slots) return fail(PHD_E_UNSUPPORTED, "feature_model 2: slot predicts (sharded step) are not supported");
-        int rc = launch_predict_dynamic(ctx);
+        int rc = launch_predict_dynamic(ctx, slots, count);
         if (rc) return rc;
     }
     const PredictCfg pc = predict_cfg(ctx->cfg, ctx->index_offset);

@@ -241,8 +241,12 @@ static DevCfg dev_cfg(const phd_slam_config& c) {
     return d;
 }
 
-/* Mixed static + dynamic update (feature_model 2; phd_mixed.hip). */
-static int launch_update_mixed(phd_ctx* ctx) {
+/* Mixed static + dynamic update (feature_model 2; phd_mixed.hip) of every
+ * particle, or (slots != NULL) a re-update of `nslots` listed slots with the
+ * sets of the last launch: same input sets, same output sets, cur and dcur
+ * unchanged (a sharded step's overflow recovery, as launch_update's).  Every
+ * prior is read through its slab reference, the sets X included. */
+static int launch_update_mixed(phd_ctx* ctx, const int* slots, int nslots) {
     const phd_slam_config& cfg = ctx->cfg;
     if (!ctx->mx.on) return fail(PHD_E_ARG, "feature_model 2 needs phd_enable_dynamic");
     if (cfg.filterType != PHD_FILTER_PHD) return fail(PHD_E_UNSUPPORTED, "feature_model 2 with the CPHD filter");
@@ -253,12 +257,19 @@ static int launch_update_mixed(phd_ctx* ctx) {
                     "the constant 0 (device_math.cuh:366-371), which would merge every dynamic component into one");
     if (cfg.distanceMetric != 0) return fail(PHD_E_UNSUPPORTED, "distance_metric must be 0 (Mahalanobis)");
     if (ctx->st.replay) return fail(PHD_E_UNSUPPORTED, "feature_model 2 in replay mode");
-    if (ctx->st.d_map_x) return fail(PHD_E_UNSUPPORTED, "feature_model 2 with migrated (sharded) particles");
-    if (ctx->n <= 0) return PHD_OK;
-    const int in_set = ctx->st.cur, out_set = in_set ^ 1;
-    const int din = ctx->mx.dcur, dout = din ^ 1;
+    if (ctx->st.d_map_x && !ctx->mx.d_dmap_x)  // (static records received before phd_enable_dynamic)
+        return fail(PHD_E_ARG, "feature_model 2: migrated particles without dynamic maps (phd_enable_dynamic comes first)");
+    const int grid = slots ? nslots : ctx->n;
+    if (grid <= 0) return PHD_OK;
+    const int in_set = slots ? ctx->st.cur ^ 1 : ctx->st.cur, out_set = in_set ^ 1;
+    const int din = slots ? ctx->mx.dcur ^ 1 : ctx->mx.dcur, dout = din ^ 1;
     MixedArgs a;
-    a.n = ctx->n;
+    a.n = grid;
+    a.slots = slots;
+    a.map_x = ctx->st.d_map_x;
+    a.size_x = ctx->st.d_size_x;
+    a.dmap_x = ctx->mx.d_dmap_x;
+    a.dsize_x = ctx->mx.d_dsize_x;
     a.cap = ctx->cap.map_capacity;
     a.dcap = ctx->mx.dcap;
     a.M = ctx->z.M;
@@ -286,7 +297,7 @@ static int launch_update_mixed(phd_ctx* ctx) {
     a.cand = ctx->mx.d_cand;
     const size_t lds = mixed_lds_bytes(a.cap, a.dcap, ctx->cap.max_measurements, a.Kcap);
     if (lds > 150 * 1024) return fail(PHD_E_CAPACITY, "feature_model 2: capacities exceed the 150 KB LDS budget");
-    const bool timed = PHD_TIMING_EVENTS && !ctx->tm.ev_a.empty() && ctx->tm.tick++ % ctx->tm.stride == 0;
+    const bool timed = PHD_TIMING_EVENTS && !ctx->tm.ev_a.empty() && !slots && ctx->tm.tick++ % ctx->tm.stride == 0;
     const int ei = ctx->tm.next;
     if (timed) HIPCHK(hipEventRecord(ctx->tm.ev_a[ei], ctx->stream));
     HIPCHK(mixed_launch_update(a, lds, ctx->stream));
@@ -295,8 +306,10 @@ static int launch_update_mixed(phd_ctx* ctx) {
         ctx->tm.next = (ei + 1) % (int)ctx->tm.ev_a.size();
         if (ctx->tm.used < (int)ctx->tm.ev_a.size()) ctx->tm.used++;
     }
+    if (slots) return PHD_OK;
     ctx->st.cur = out_set;
     ctx->mx.dcur = dout;
+    ctx->mx.x_live = false;  // every reference is the identity again: none names the sets X
     return PHD_OK;
 }
 
@@ -326,8 +339,7 @@ int launch_update(phd_ctx* ctx, const FusedPredict* fused, const int* slots, int
     if (!done) done = &done_here;
     const phd_slam_config& cfg = ctx->cfg;
     if (cfg.featureModel == PHD_FEATURE_MIXED) {
-        if (slots) return fail(PHD_E_UNSUPPORTED, "feature_model 2: slot updates (sharded step) are not supported");
-        return launch_update_mixed(ctx);
+        return launch_update_mixed(ctx, slots, nslots);
     }
     if (cfg.featureModel != PHD_FEATURE_STATIC)
         return fail(PHD_E_UNSUPPORTED,

@@ -183,6 +183,7 @@ struct ShardPlan {
     int world = 0, rank = 0;
     int pend_count = 0;          // pending slots of the last polled plan
     int max_blocks = 0;          // workgroups of k_shard_plan resident at once (0: not queried)
+    int rec_dcap = 0;            // dynamic capacity of the record size phd_record_bytes last returned (0: the static record)
     phd::Event ev_logw, ev_plan;
     hipStream_t stream = nullptr;
 };
@@ -201,6 +202,12 @@ struct Mixed {
     int dcap = 0, dcur = 0;
     phd::DevBuf<float> d_dmap[2];
     phd::DevBuf<int> d_dsize[2];
+    // dynamic migration set X, the twin of Store::d_map_x / d_size_x (same slab
+    // ids: bit 30 of d_src[p] selects both), allocated with the first receive
+    // on a mixed context (phd_capi_shard.hip)
+    phd::DevBuf<float> d_dmap_x;
+    phd::DevBuf<int> d_dsize_x;
+    bool x_live = false;  // a receive since the last full update: references may name set X (the predict advances it)
     phd::DevBuf<float> d_ekf, d_cand;
 };
 
@@ -306,6 +313,20 @@ struct UpdateDone {
 };
 int launch_update(phd_ctx* ctx, const FusedPredict* fused = nullptr, const int* slots = nullptr, int nslots = 0,
                   const RsBeside* rs = nullptr, UpdateDone* done = nullptr);
+
+/* phd_capi_shard.hip */
+/* dynamic capacity a migration record carries: 0 unless feature_model 2 (with
+ * the PHD filter: the mixed model has no CPHD, so no cardinality rows) after
+ * phd_enable_dynamic — then the record is record_words_mixed (phd_slab.h) */
+inline int rec_dcap(const phd_ctx* c) {
+    return c->cfg_set && c->cfg.featureModel == PHD_FEATURE_MIXED && c->cfg.filterType == PHD_FILTER_PHD && c->mx.on
+               ? c->mx.dcap
+               : 0;
+}
+/* the dynamic migration set X beside the static one, sized like it (n slabs,
+ * empty): with the first receive, and when phd_enable_dynamic changes the
+ * capacity of a context that holds migrated slabs */
+int ensure_dyn_x(phd_ctx* c);
 
 /* phd_capi_step.hip */
 phd::PredictCfg predict_cfg(const phd_slam_config& c, int index_offset);

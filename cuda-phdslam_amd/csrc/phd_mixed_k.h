@@ -15,11 +15,12 @@
 #include <string>
 
 #include "phd_mixed.h"
+#include "phd_slab.h"
 #include "phd_types.h"
 
 namespace phd {
 
-#define PHD_DYN_FIELDS 21
+/* (PHD_DYN_FIELDS, the floats of one dynamic component: phd_slab.h) */
 /* status bits (phd_kernels.h PHD_ST_CANDIDATE_OVERFLOW / PHD_ST_MAP_OVERFLOW) */
 #define PHD_ST_CANDIDATE_OVERFLOW_MX 2
 #define PHD_ST_MAP_OVERFLOW_MX 4
@@ -28,16 +29,21 @@ struct MixedArgs {
     int n;            // particles (one workgroup each)
     int cap, dcap;    // static / dynamic slab capacities
     int M, Kcap;      // measurements, candidate capacity per map
-    const int* src;   // slab of particle n in the input sets
-    int* src_reset;   // posterior of particle n -> output slab n
+    const int* slots; // NULL: block b does particle b; else particle slots[b] (n blocks)
+    const int* src;   // slab reference of particle p: the input sets, or (bit 30) the sets X
+    int* src_reset;   // posterior of particle p -> output slab p
     const float* map_in;
     float* map_out;
     const int* size_in;
     int* size_out;
+    const float* map_x;  // static migration set X (NULL before the first receive)
+    const int* size_x;
     const float* dmap_in;
     float* dmap_out;
     const int* dsize_in;
     int* dsize_out;
+    const float* dmap_x;  // dynamic migration set X
+    const int* dsize_x;
     const phd_pose* poses;
     float* logw;
     float* delta;
@@ -61,11 +67,54 @@ hipError_t mixed_launch_update(const MixedArgs& a, size_t lds, hipStream_t s);
 /* one predictMapMixed over `nslabs` slabs: set in -> set out */
 hipError_t mixed_launch_predict(int nslabs, int dcap, const float* din, const int* dsize_in, float* dout,
                                 int* dsize_out, const phd_mx_cfg& c, hipStream_t s);
+/* predictMapMixed of the dynamic migration set X, in place (each thread reads
+ * and writes its own component only).  slots == NULL: every one of the `count`
+ * slabs of X.  Else one workgroup per listed slot, `count` of them: the slab
+ * the slot's reference names in X, predicted by the first of the consecutive
+ * slots that name it (a sharded plan lists its pending slots in slot order and
+ * the slots of one record are consecutive: once per slab); a slot that does
+ * not refer to X is left alone (its slab of the current set went with the
+ * full predict). */
+hipError_t mixed_launch_predict_x(const int* slots, int count, const int* src, int dcap, float* dmap_x,
+                                  const int* dsize_x, const phd_mx_cfg& c, hipStream_t s);
 hipError_t mixed_set_lds_limit();
+
+/* ---- migration records of a mixed context (phd_slab.h: record_words_mixed) ----
+ * The forms of phd_kernels.hip's k_pack / k_unpack / k_unpack_slots /
+ * k_pack_blocks / k_unpack_blocks with the same arguments and the same record
+ * numbering, for records that carry the dynamic map after the static one; one
+ * workgroup per record at a time, the rows copied as 16-byte vectors where the
+ * alignment allows it, the first dsize components of each row only. */
+struct MixedStore {
+    int cap, dcap;
+    int* src;
+    const float* map_in;   // current static set
+    const int* size_in;
+    float* map_x;          // static set X
+    int* size_x;
+    const float* dmap_in;  // current dynamic set
+    const int* dsize_in;
+    float* dmap_x;         // dynamic set X
+    int* dsize_x;
+    phd_pose* pose;
+    float* logw;
+};
+hipError_t mixed_launch_pack(const MixedStore& S, int grid, const int* dcount, const int* src_idx, int count,
+                             int logw_set, float logw_value, float* rec, hipStream_t s);
+hipError_t mixed_launch_unpack(const MixedStore& S, const float* rec, const int* dst_idx, int count, hipStream_t s);
+hipError_t mixed_launch_unpack_slots(const MixedStore& S, const float* rec, const int* slot_rec, int nslots,
+                                     int first_slot, hipStream_t s);
+hipError_t mixed_launch_pack_blocks(const MixedStore& S, int grid, const int* mig, int world, const int* send_src,
+                                    int block_records, int ovf_capacity, float logw_value, float* blocks, float* ovf,
+                                    int* ovf_flag, hipStream_t s);
+hipError_t mixed_launch_unpack_blocks(const MixedStore& S, int grid, const float* blocks, const float* ovf,
+                                      int block_records, int overflow, const int* mig, int world, int rank,
+                                      const int* recv_rec, int n, hipStream_t s);
 /* EAP map of the dynamic maps of n particles (exp_map_dynamic): the component
- * count (nothing copied when out is NULL or too small), -1 on a HIP error */
-long mixed_expected_map_dynamic(hipStream_t st, const int* d_src, const float* d_dmap, const int* d_dsize, int n,
-                                int dcap, const float* d_logw, float T, phd_gaussian4d* out, long out_cap,
+ * count (nothing copied when out is NULL or too small), -1 on a HIP error;
+ * d_dmap_x / d_dsize_x: the dynamic set X (NULL: no reference names it) */
+long mixed_expected_map_dynamic(hipStream_t st, const int* d_src, const float* d_dmap, const int* d_dsize,
+                                const float* d_dmap_x, const int* d_dsize_x, int n, int dcap, const float* d_logw, float T, phd_gaussian4d* out, long out_cap,
                                 std::string& err);
 
 }  // namespace phd

@@ -45,6 +45,29 @@ __host__ __device__ inline size_t record_words(int cap, int cn_stride) {
     return 8 + (size_t)PHD_NF * cap + 2 * (size_t)cn_stride;
 }
 
+/* Mixed contexts (feature_model 2 after phd_enable_dynamic, dcap > 0): the
+ * record above, padded to a multiple of 4 words, then the dynamic part
+ *   [dsize | 3 reserved words (0) | dmap PHD_DYN_FIELDS * dcap]
+ * (rows [w | m0..m3 | c0..c15] of dcap floats, the first dsize of each live),
+ * the whole padded to a multiple of 4 words again: in a 16-byte aligned buffer
+ * every record, every dynamic part and (dcap a multiple of 4) every row starts
+ * on 16 bytes.  dcap == 0: the static / CPHD record, unchanged. */
+#define PHD_DYN_FIELDS 21
+#define PHD_REC_DYN_HEAD 4 /* words before the dynamic rows */
+/* the dynamic map a reference names: the slab of the same id in the current
+ * dynamic set or in dynamic set X (its size: slab_size on the dynamic sizes) */
+template <class T>
+__host__ __device__ inline T* dyn_slab_map(int sref, T* dmap_in, T* dmap_x, int dcap) {
+    return (slab_in_x(sref) ? dmap_x : dmap_in) + (size_t)slab_index(sref) * PHD_DYN_FIELDS * dcap;
+}
+__host__ __device__ inline size_t record_dyn_offset(int cap, int cn_stride) {
+    return (record_words(cap, cn_stride) + 3) & ~(size_t)3;
+}
+__host__ __device__ inline size_t record_words_mixed(int cap, int cn_stride, int dcap) {
+    if (dcap <= 0) return record_words(cap, cn_stride);
+    return (record_dyn_offset(cap, cn_stride) + PHD_REC_DYN_HEAD + (size_t)PHD_DYN_FIELDS * dcap + 3) & ~(size_t)3;
+}
+
 /* One workgroup writes particle `ps`'s record at o: its map `s`, and its
  * cardinality coefficients `cs` when cn_stride != 0. */
 __device__ __forceinline__ void record_write(float* o, int cap, int cn_stride, const phd_pose* ps, float logw,

@@ -88,6 +88,8 @@ SIGNATURES = {
     "phd_set_index_offset": (ctypes.c_int, [_vp, ctypes.c_int]),
     "phd_fill_log_weights": (ctypes.c_int, [_vp, ctypes.c_float]),
     "phd_record_bytes": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_size_t)]),
+    "phd_record_layout_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.POINTER(ctypes.c_size_t)]),
     "phd_pack_particles": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp]),
     "phd_unpack_particles": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int]),
     "phd_expected_pose": (ctypes.c_int, [_vp, _vp, _c_int_p]),

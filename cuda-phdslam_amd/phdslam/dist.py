@@ -188,6 +188,10 @@ class ShardedFilter:
     before constructing: the plan stream beside part C is set up only for the
     split form found here (a later change stays correct — the all-gather waits
     on phd_wait_logw, which every form records — without the overlap).
+    The record buffers are sized here, from f.record_bytes(): with the mixed
+    model (feature_model 2) call f.enable_dynamic first — its records carry the
+    dynamic map — and construct again after another dynamic capacity (the plan
+    refuses records of a size the buffers were not made for).
     """
 
     def __init__(self, f, dist, device, world=None, rank=None, seed=0x9e3779b97f4a7c15, block_records=4, comm=None,

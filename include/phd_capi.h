@@ -104,7 +104,13 @@ int phd_export_maps(phd_ctx* ctx, int n, const int* offsets, phd_gaussian2d* map
  * maps' slab references, so resampling and n_predict_particles carry them.
  * phd_load_dynamic_maps needs particle i to own slab i (after
  * phd_load_particles or an update).  Not supported with feature_model 2: CPHD,
- * replay mode, sharded steps.  Synchronise (except phd_predict_dynamic). */
+ * replay mode, distance_metric 1.  The sharded step (below) supports it with
+ * the PHD filter: a particle's dynamic map travels in its migration record
+ * into a dynamic migration set beside the static one, and every reader here
+ * follows the slab reference into it; phd_enable_dynamic comes before the
+ * record buffers are sized (phd_record_bytes), and with another capacity on a
+ * context that holds migrated slabs it leaves them empty dynamic maps, like
+ * every other particle's.  Synchronise (except phd_predict_dynamic). */
 int phd_enable_dynamic(phd_ctx* ctx, int dyn_capacity);
 int phd_load_dynamic_maps(phd_ctx* ctx, int n, const phd_gaussian4d* maps, const int* offsets);
 int phd_dynamic_sizes(phd_ctx* ctx, int* sizes);
@@ -289,8 +295,26 @@ int phd_update_pending(phd_ctx* ctx, const phd_ackerman_control* u, int do_predi
 int phd_set_index_offset(phd_ctx* ctx, int offset);
 /* Set every log-weight to `value` (e.g. -log N after a sharded resample). */
 int phd_fill_log_weights(phd_ctx* ctx, float value);
-/* Fixed-size particle records for migration between ranks. */
+/* Fixed-size particle records for migration between ranks, in 32-bit words:
+ *   [pose 6 | log-weight | size | map 7 * map_capacity]
+ * (rows w mx my P00 P10 P01 P11, the first `size` of each live), then on a
+ * CPHD context the cardinality coefficients (doubles).  A mixed context
+ * (feature_model 2 after phd_enable_dynamic) pads this to a multiple of 4
+ * words and appends its particle's dynamic map,
+ *   [dsize | 3 reserved (0) | dmap 21 * dyn_capacity]
+ * (rows w m0..m3 c0..c15, the first `dsize` of each live), padded to a multiple
+ * of 4 words again; every other context's record is unchanged.
+ * phd_record_layout_bytes is that arithmetic alone (cn_stride: doubles of
+ * cardinality coefficients, dyn_capacity 0: no dynamic part; no device).
+ * phd_record_bytes is the context's record size NOW, and what the caller sizes
+ * its buffers by: on a mixed context call phd_enable_dynamic first, then
+ * phd_record_bytes (phdslam.dist.ShardedFilter and phd_group read it when
+ * they are constructed).  Every entry point that reads or writes records
+ * (the plans, the receives, pack / unpack) returns PHD_E_ARG, before it
+ * enqueues anything, when the dynamic capacity is no longer the one
+ * phd_record_bytes last reported. */
 int phd_record_bytes(const phd_ctx* ctx, size_t* bytes);
+int phd_record_layout_bytes(int map_capacity, int cn_stride, int dyn_capacity, size_t* bytes);
 int phd_pack_particles(phd_ctx* ctx, const int* dev_src_idx, int count, void* dev_records);
 int phd_unpack_particles(phd_ctx* ctx, const void* dev_records, const int* dev_dst_idx, int count);
 
@@ -430,7 +454,7 @@ int phd_trace_shape(phd_ctx* ctx, int* capacity, int* map_snapshot_cap, int* car
  * 2), PHD_TRACE_CARD_DIST (the mixed model has no CPHD), n_predict_particles
  * > 1; from a traced phd_step after feature_model or the dynamic capacity
  * (phd_enable_dynamic) changed — enable the trace again; and from
- * phd_trace_shard_pack / _append (the sharded step does not support
+ * phd_trace_shard_pack / _append (the sharded trace does not support
  * feature_model 2).  Synchronises (an allocation, not a step). */
 int phd_trace_enable_mixed(phd_ctx* ctx, int capacity, int map_snapshot_cap, int dyn_snapshot_cap, unsigned flags);
 /* The dyn records [first, first + count) into records (count) and dmaps (count

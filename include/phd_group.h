@@ -45,7 +45,10 @@ typedef struct phd_group phd_group;
  * before this call: the plan stream beside part C is set up only for a split
  * update found here.  A later change of form stays correct (the all-gather
  * waits on phd_wait_logw, which every form records) but loses or gains no
- * overlap until the group is re-created. */
+ * overlap until the group is re-created.  The record buffers are sized here by
+ * phd_record_bytes: on a mixed context (feature_model 2) phd_enable_dynamic
+ * comes before this call, and the group is re-created after another dynamic
+ * capacity (the step then fails with PHD_E_ARG, nothing written). */
 int phd_group_create(phd_group** out, int world, phd_ctx* const* ctxs, const int* devices, int block_records,
                      uint64_t seed);
 /* One process per GPU: this process's shard `ctx` (on `device`) as rank `rank`
