@@ -24,7 +24,7 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(REPO, "build", "obj")
 OUT = os.path.join(HERE, "phdslam", "libphdslam.so")
-SOURCES = ["phd_kernels.hip", "phd_terms.hip", "phd_eap.hip", "phd_mixed.hip", "phd_trace.hip", "phd_capi_ctx.hip", "phd_capi_update.hip",
+SOURCES = ["phd_kernels.hip", "phd_terms.hip", "phd_eap.hip", "phd_mixed.hip", "phd_records.hip", "phd_trace.hip", "phd_capi_ctx.hip", "phd_capi_update.hip",
            "phd_capi_step.hip", "phd_capi_shard.hip", "phd_capi_trace.hip", "phd_capi_estimate.hip", "phd_config.cpp",
            "phd_synth.cpp", "phd_io.cpp", "phdfilter_shim.cpp"]
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")

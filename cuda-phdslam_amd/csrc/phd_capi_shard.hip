@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "phd_ctx.h"
+#include "phd_records.h"
 
 using namespace phd;
 
@@ -37,17 +38,20 @@ int ensure_dyn_x(phd_ctx* c) {
     return PHD_OK;
 }
 
-/* The record kernels of a mixed context (phd_mixed.hip) see the store through
- * this; the static kernels' arguments otherwise. */
-static MixedStore mixed_store(const phd_ctx* c) {
-    MixedStore S;
+/* The record kernels (phd_records.hip) see the store through this, as it is
+ * when the launch is enqueued. */
+static RecordStore record_store(const phd_ctx* c) {
+    RecordStore S;
     S.cap = c->cap.map_capacity;
-    S.dcap = c->mx.dcap;
+    S.cn_stride = rec_cn_stride(c);
+    S.dcap = rec_dcap(c);
     S.src = c->st.d_src;
     S.map_in = c->st.d_map[c->st.cur];
     S.size_in = c->st.d_size[c->st.cur];
     S.map_x = c->st.d_map_x;
     S.size_x = c->st.d_size_x;
+    S.cn = c->cn.d_coef;
+    S.cn_x = c->cn.d_x;
     S.dmap_in = c->mx.d_dmap[c->mx.dcur];
     S.dsize_in = c->mx.d_dsize[c->mx.dcur];
     S.dmap_x = c->mx.d_dmap_x;
@@ -253,17 +257,9 @@ int phd_shard_resample(phd_ctx* ctx, float* dev_w_all, int world, int rank, uint
         if (ensure_cn(ctx)) return PHD_E_HIP;
         // records this rank sends (count on the device) from the pre-resample
         // store; they carry the new log-weight
-        if (rec_dcap(ctx))
-            HIPCHK(mixed_launch_pack(mixed_store(ctx), std::min(send_capacity, 256), (const int*)(ctx->sh.d_mig + 3 * world),
-                                     (const int*)dev_send_src, send_capacity, 1, new_log_weight,
-                                     (float*)dev_send_records, ctx->stream));
-        else
-            hipLaunchKernelGGL(k_pack, dim3(std::min(send_capacity, 256)), dim3(256), 0, ctx->stream,
-                               (const int*)(ctx->sh.d_mig + 3 * world), (const int*)dev_send_src, send_capacity,
-                               ctx->cap.map_capacity, ctx->st.d_src, ctx->st.d_map[ctx->st.cur], ctx->st.d_size[ctx->st.cur],
-                               ctx->st.d_map_x, ctx->st.d_size_x, ctx->st.d_pose, ctx->st.d_logw, 1, new_log_weight,
-                               ctx->cn.d_coef, ctx->cn.d_x, rec_cn_stride(ctx), (float*)dev_send_records);
-        HIPCHK(hipGetLastError());
+        HIPCHK(records_pack(record_store(ctx), std::min(send_capacity, 256), (const int*)(ctx->sh.d_mig + 3 * world),
+                            (const int*)dev_send_src, send_capacity, 1, new_log_weight, (float*)dev_send_records,
+                            ctx->stream));
     }
     int* h = ctx->sh.h_mig;  // (written by the plan's tail)
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -339,21 +335,11 @@ int phd_shard_resample_async(phd_ctx* ctx, float* dev_w_all, int world, int rank
                                dev_send_src, dev_recv_rec, new_log_weight, block_records);
         if (rc) return rc;
     }
-    if (world > 1 && rec_dcap(ctx)) {  // (mixed: the records carry the dynamic maps, phd_mixed.hip)
-        HIPCHK(mixed_launch_pack_blocks(mixed_store(ctx), std::min(ctx->n, 256), (const int*)ctx->sh.d_mig, world,
-                                        (const int*)dev_send_src, block_records, overflow_capacity, new_log_weight,
-                                        (float*)dev_send_blocks, (float*)dev_overflow,
-                                        ctx->sh.h_mig_dev + 3 * world + MIG_OVF_CAP, ctx->stream));
-    } else if (world > 1) {  // records from the pre-resample store (the pointers are swapped below)
-        hipLaunchKernelGGL(k_pack_blocks, dim3(std::min(ctx->n, 256)), dim3(256), 0, ctx->stream,
-                           (const int*)ctx->sh.d_mig, world, (const int*)dev_send_src, block_records, overflow_capacity,
-                           ctx->cap.map_capacity, (const int*)ctx->st.d_src, (const float*)ctx->st.d_map[ctx->st.cur],
-                           (const int*)ctx->st.d_size[ctx->st.cur], (const float*)ctx->st.d_map_x, (const int*)ctx->st.d_size_x,
-                           (const phd_pose*)ctx->st.d_pose, new_log_weight, (const double*)ctx->cn.d_coef,
-                           (const double*)ctx->cn.d_x, rec_cn_stride(ctx), (float*)dev_send_blocks,
-                           (float*)dev_overflow, ctx->sh.h_mig_dev + 3 * world + MIG_OVF_CAP);
-        HIPCHK(hipGetLastError());
-    }
+    if (world > 1)  // records from the pre-resample store (the pointers are swapped below)
+        HIPCHK(records_pack_blocks(record_store(ctx), std::min(ctx->n, 256), (const int*)ctx->sh.d_mig, world,
+                                   (const int*)dev_send_src, block_records, overflow_capacity, new_log_weight,
+                                   (float*)dev_send_blocks, (float*)dev_overflow,
+                                   ctx->sh.h_mig_dev + 3 * world + MIG_OVF_CAP, ctx->stream));
     // the tail wrote the remapped store (the identity without a resample): swap it in
     std::swap(ctx->st.d_pose, ctx->st.d_tmp_pose);
     std::swap(ctx->st.d_src, ctx->st.d_tmp_src);
@@ -399,16 +385,9 @@ int phd_shard_receive_blocks(phd_ctx* ctx, const void* dev_recv_blocks, int bloc
     if (int rc0 = record_size_known(ctx)) return rc0;
     if (ensure_x(ctx)) return PHD_E_HIP;
     ctx->st.src_fresh = false;
-    if (rec_dcap(ctx))
-        HIPCHK(mixed_launch_unpack_blocks(mixed_store(ctx), std::min(ctx->n, 256), (const float*)dev_recv_blocks,
-                                          (const float*)nullptr, block_records, 0, (const int*)ctx->sh.d_mig,
-                                          ctx->sh.world, ctx->sh.rank, dev_recv_rec, ctx->n, ctx->stream));
-    else
-        hipLaunchKernelGGL(k_unpack_blocks, dim3(std::min(ctx->n, 256)), dim3(256), 0, ctx->stream, (const float*)dev_recv_blocks,
-                           (const float*)nullptr, block_records, 0, (const int*)ctx->sh.d_mig, ctx->sh.world,
-                           ctx->sh.rank, dev_recv_rec, ctx->n, ctx->cap.map_capacity, ctx->st.d_map_x,
-                           ctx->st.d_size_x, ctx->st.d_src, ctx->st.d_pose, ctx->st.d_logw, ctx->cn.d_x, rec_cn_stride(ctx));
-    HIPCHK(hipGetLastError());
+    HIPCHK(records_unpack_blocks(record_store(ctx), std::min(ctx->n, 256), (const float*)dev_recv_blocks,
+                                 (const float*)nullptr, block_records, 0, (const int*)ctx->sh.d_mig, ctx->sh.world,
+                                 ctx->sh.rank, dev_recv_rec, ctx->n, ctx->stream));
     return PHD_OK;
 }
 
@@ -460,18 +439,10 @@ int phd_shard_receive_overflow(phd_ctx* ctx, const void* dev_recv_overflow, int 
     if (set_device(ctx)) return PHD_E_HIP;
     if (int rc0 = record_size_known(ctx)) return rc0;
     ctx->st.src_fresh = false;
-    if (rec_dcap(ctx)) {
-        if (ensure_x(ctx)) return PHD_E_HIP;  // (the sets X exist since the blocks' receive; marks them live again)
-        HIPCHK(mixed_launch_unpack_blocks(mixed_store(ctx), std::min(ctx->n, 256), (const float*)nullptr,
-                                          (const float*)dev_recv_overflow, block_records, 1, (const int*)ctx->sh.d_mig,
-                                          ctx->sh.world, ctx->sh.rank, dev_recv_rec, ctx->n, ctx->stream));
-    } else {
-        hipLaunchKernelGGL(k_unpack_blocks, dim3(std::min(ctx->n, 256)), dim3(256), 0, ctx->stream, (const float*)nullptr,
-                           (const float*)dev_recv_overflow, block_records, 1, (const int*)ctx->sh.d_mig, ctx->sh.world,
-                           ctx->sh.rank, dev_recv_rec, ctx->n, ctx->cap.map_capacity, ctx->st.d_map_x,
-                           ctx->st.d_size_x, ctx->st.d_src, ctx->st.d_pose, ctx->st.d_logw, ctx->cn.d_x, rec_cn_stride(ctx));
-    }
-    HIPCHK(hipGetLastError());
+    if (ensure_x(ctx)) return PHD_E_HIP;  // (the sets X exist since the blocks' receive; mixed: marks them live again)
+    HIPCHK(records_unpack_blocks(record_store(ctx), std::min(ctx->n, 256), (const float*)nullptr,
+                                 (const float*)dev_recv_overflow, block_records, 1, (const int*)ctx->sh.d_mig,
+                                 ctx->sh.world, ctx->sh.rank, dev_recv_rec, ctx->n, ctx->stream));
     return PHD_OK;
 }
 
@@ -500,14 +471,8 @@ int phd_shard_receive(phd_ctx* ctx, const void* dev_records, const int* dev_recv
     if (set_device(ctx)) return PHD_E_HIP;
     if (int rc0 = record_size_known(ctx)) return rc0;
     if (ensure_x(ctx)) return PHD_E_HIP;
-    if (rec_dcap(ctx))
-        HIPCHK(mixed_launch_unpack_slots(mixed_store(ctx), (const float*)dev_records, dev_recv_rec, n_slots, first_slot,
-                                         ctx->stream));
-    else
-        hipLaunchKernelGGL(k_unpack_slots, dim3(n_slots), dim3(256), 0, ctx->stream, (const float*)dev_records,
-                           dev_recv_rec, n_slots, first_slot, ctx->cap.map_capacity, ctx->st.d_map_x, ctx->st.d_size_x,
-                           ctx->st.d_src, ctx->st.d_pose, ctx->st.d_logw, ctx->cn.d_x, rec_cn_stride(ctx));
-    HIPCHK(hipGetLastError());
+    HIPCHK(records_unpack_slots(record_store(ctx), (const float*)dev_records, dev_recv_rec, n_slots, first_slot,
+                                ctx->stream));
     return PHD_OK;
 }
 
@@ -547,15 +512,8 @@ int phd_pack_particles(phd_ctx* ctx, const int* dev_src_idx, int count, void* de
     if (set_device(ctx)) return PHD_E_HIP;
     if (int rc0 = record_size_known(ctx)) return rc0;
     if (ensure_cn(ctx)) return PHD_E_HIP;
-    if (rec_dcap(ctx))
-        HIPCHK(mixed_launch_pack(mixed_store(ctx), count, (const int*)nullptr, dev_src_idx, count, 0, 0.f,
-                                 (float*)dev_records, ctx->stream));
-    else
-        hipLaunchKernelGGL(k_pack, dim3(count), dim3(256), 0, ctx->stream, (const int*)nullptr, dev_src_idx, count,
-                           ctx->cap.map_capacity, ctx->st.d_src, ctx->st.d_map[ctx->st.cur], ctx->st.d_size[ctx->st.cur], ctx->st.d_map_x,
-                           ctx->st.d_size_x, ctx->st.d_pose, ctx->st.d_logw, 0, 0.f, ctx->cn.d_coef, ctx->cn.d_x,
-                           rec_cn_stride(ctx), (float*)dev_records);
-    HIPCHK(hipGetLastError());
+    HIPCHK(records_pack(record_store(ctx), count, (const int*)nullptr, dev_src_idx, count, 0, 0.f, (float*)dev_records,
+                        ctx->stream));
     return PHD_OK;
 }
 
@@ -566,13 +524,7 @@ int phd_unpack_particles(phd_ctx* ctx, const void* dev_records, const int* dev_d
     if (set_device(ctx)) return PHD_E_HIP;
     if (int rc0 = record_size_known(ctx)) return rc0;
     if (ensure_x(ctx)) return PHD_E_HIP;
-    if (rec_dcap(ctx))
-        HIPCHK(mixed_launch_unpack(mixed_store(ctx), (const float*)dev_records, dev_dst_idx, count, ctx->stream));
-    else
-        hipLaunchKernelGGL(k_unpack, dim3(count), dim3(256), 0, ctx->stream, (const float*)dev_records, dev_dst_idx,
-                           (const int*)nullptr, count, ctx->cap.map_capacity, ctx->st.d_map_x, ctx->st.d_size_x, ctx->st.d_src,
-                           ctx->st.d_pose, ctx->st.d_logw, ctx->cn.d_x, rec_cn_stride(ctx));
-    HIPCHK(hipGetLastError());
+    HIPCHK(records_unpack(record_store(ctx), (const float*)dev_records, dev_dst_idx, count, ctx->stream));
     return PHD_OK;
 }
 

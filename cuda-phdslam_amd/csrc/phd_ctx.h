@@ -317,7 +317,7 @@ int launch_update(phd_ctx* ctx, const FusedPredict* fused = nullptr, const int* 
 /* phd_capi_shard.hip */
 /* dynamic capacity a migration record carries: 0 unless feature_model 2 (with
  * the PHD filter: the mixed model has no CPHD, so no cardinality rows) after
- * phd_enable_dynamic — then the record is record_words_mixed (phd_slab.h) */
+ * phd_enable_dynamic — then the record is record_words_mixed (phd_records.h) */
 inline int rec_dcap(const phd_ctx* c) {
     return c->cfg_set && c->cfg.featureModel == PHD_FEATURE_MIXED && c->cfg.filterType == PHD_FILTER_PHD && c->mx.on
                ? c->mx.dcap

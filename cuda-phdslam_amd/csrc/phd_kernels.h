@@ -532,21 +532,6 @@ struct ShardPlanArgs {
 __global__ void k_shard_plan(ShardPlanArgs a);
 /* k_rs_step's arguments: k_rs_sumcdf's and k_rs_search's (remap form) */
 __global__ void k_rs_step(RsStepArgs a);
-__global__ void k_pack_blocks(const int* mig, int world, const int* send_src, int block_records, int ovf_capacity,
-                              int cap, const int* src, const float* map_in, const int* size_in, const float* map_x,
-                              const int* size_x, const phd_pose* pose, float logw_value, const double* cn,
-                              const double* cn_x, int cn_stride, float* blocks, float* ovf, int* ovf_flag);
-__global__ void k_unpack_blocks(const float* blocks, const float* ovf, int block_records, int overflow, const int* mig,
-                                int world, int rank, const int* recv_rec, int n, int cap, float* map_x, int* size_x,
-                                int* src, phd_pose* pose, float* logw, double* cn_x, int cn_stride);
-__global__ void k_unpack_slots(const float* rec, const int* slot_rec, int nslots, int first_slot, int cap, float* map_x,
-                               int* size_x, int* src, phd_pose* pose, float* logw, double* cn_x, int cn_stride);
-__global__ void k_pack(const int* dcount, const int* src_idx, int count, int cap, const int* src, const float* map_in,
-                       const int* size_in, const float* map_x, const int* size_x, const phd_pose* pose,
-                       const float* logw, int logw_set, float logw_value, const double* cn, const double* cn_x,
-                       int cn_stride, float* rec);
-__global__ void k_unpack(const float* rec, const int* dst_idx, const int* x_slot, int count, int cap, float* map_x,
-                         int* size_x, int* src, phd_pose* pose, float* logw, double* cn_x, int cn_stride);
 __global__ void k_expected_pose(const float* logw, const phd_pose* pose, int n, float* out);
 __global__ void k_cardinality(const int* src, const float* map_in, const int* size_in, const float* map_x,
                               const int* size_x, int n, int cap, float* cn);

@@ -13,8 +13,8 @@
  *       per particle; the F×M pair space never touches HBM.
  *   k_normalize                        — phdfilter.cu:3748-3755 + main.cpp:1281-1284
  *   k_resample / k_apply_parents       — main.cpp:453-501 + slamtypes.h:313-333 (index remap)
- *   k_pack / k_unpack                  — particle records for cross-rank migration
- *   k_migration_plan / k_unpack_slots  — keep / send / receive slots of a sharded resample
+ *   k_migration_plan                   — keep / send / receive slots of a sharded resample
+ *       (its migration records: phd_records.hip)
  *   k_expected_pose / k_cardinality    — main.cpp:331-361
  */
 #include <hip/hip_runtime.h>
@@ -3951,128 +3951,6 @@ __global__ void __launch_bounds__(256)
             atomicOr(err, PHD_ST_MAP_OVERFLOW);
             atomicAdd(err + 3, 1);
         }
-    }
-}
-
-/* `dcount` (device) overrides `count` when given (records beyond it are not
- * written); the grid strides over records.  `logw_set` != 0 writes `logw_value`
- * as the record's log-weight (a sharded resample's -log N). */
-__global__ void __launch_bounds__(256)
-    k_pack(const int* __restrict__ dcount, const int* __restrict__ src_idx, int count, int cap,
-           const int* __restrict__ src, const float* __restrict__ map_in, const int* __restrict__ size_in,
-           const float* __restrict__ map_x, const int* __restrict__ size_x, const phd_pose* __restrict__ pose,
-           const float* __restrict__ logw, int logw_set, float logw_value, const double* __restrict__ cn,
-           const double* __restrict__ cn_x, int cn_stride, float* __restrict__ rec) {
-    if (dcount) count = min(*dcount, count);
-    const size_t rw = record_words(cap, cn_stride);
-    for (int r = blockIdx.x; r < count; r += gridDim.x) {
-        const int p = src_idx[r];
-        const int sref = src[p];
-        record_write(rec + (size_t)r * rw, cap, cn_stride, &pose[p], logw_set ? logw_value : logw[p],
-                     slab_of(sref, map_in, size_in, map_x, size_x, cap), slab_cn(sref, cn, cn_x, cn_stride));
-    }
-}
-
-/* Unpack record r into migration slab x_slot[r] of set X and point particle dst_idx[r] at it. */
-__global__ void __launch_bounds__(256)
-    k_unpack(const float* __restrict__ rec, const int* __restrict__ dst_idx, const int* __restrict__ x_slot, int count,
-             int cap, float* __restrict__ map_x, int* __restrict__ size_x, int* __restrict__ src,
-             phd_pose* __restrict__ pose, float* __restrict__ logw, double* __restrict__ cn_x, int cn_stride) {
-    const int r = blockIdx.x;
-    if (r >= count) return;
-    const int p = dst_idx[r];
-    const int xs = x_slot ? x_slot[r] : r;
-    const float* o = rec + (size_t)r * record_words(cap, cn_stride);
-    record_read(o, cap, cn_stride, p, xs, true, map_x, size_x, src, pose, logw, cn_x);
-}
-
-/* Receive side of a sharded resample: slot first_slot + i takes record
- * slot_rec[i]; the first slot of each record copies its map into migration slab
- * slot_rec[i] of set X, and every slot of the record points at that slab. */
-__global__ void __launch_bounds__(256)
-    k_unpack_slots(const float* __restrict__ rec, const int* __restrict__ slot_rec, int nslots, int first_slot, int cap,
-                   float* __restrict__ map_x, int* __restrict__ size_x, int* __restrict__ src,
-                   phd_pose* __restrict__ pose, float* __restrict__ logw, double* __restrict__ cn_x, int cn_stride) {
-    const int i = blockIdx.x;
-    if (i >= nslots) return;
-    const int r = slot_rec[i];
-    const int p = first_slot + i;
-    const float* o = rec + (size_t)r * record_words(cap, cn_stride);
-    record_read(o, cap, cn_stride, p, r, !(i > 0 && slot_rec[i - 1] == r), map_x, size_x, src, pose, logw, cn_x);
-}
-
-/* The sender's records in fixed blocks: record t of send_src goes to rank d
- * (records are grouped by destination, mig[world + d] each) as its r-th record:
- * block slot d * block_records + r, or — beyond the block — position
- * Σ_{d' < d} max(sent_d' - K, 0) + r - K of the overflow buffer (exchanged
- * only when a read-back shows it used).  Records carry the new log-weight. */
-__global__ void __launch_bounds__(256)
-    k_pack_blocks(const int* __restrict__ mig, int world, const int* __restrict__ send_src, int block_records,
-                  int ovf_capacity, int cap, const int* __restrict__ src, const float* __restrict__ map_in,
-                  const int* __restrict__ size_in, const float* __restrict__ map_x, const int* __restrict__ size_x,
-                  const phd_pose* __restrict__ pose, float logw_value, const double* __restrict__ cn,
-                  const double* __restrict__ cn_x, int cn_stride, float* __restrict__ blocks,
-                  float* __restrict__ ovf, int* __restrict__ ovf_flag) {
-    const int count = mig[3 * world + MIG_SENT];
-    const size_t rw = record_words(cap, cn_stride);
-    const int K = block_records;
-    for (int t = blockIdx.x; t < count; t += gridDim.x) {
-        int d = 0, first = 0, ofirst = 0;
-        while (d < world - 1 && t >= first + mig[world + d]) {
-            first += mig[world + d];
-            ofirst += max(mig[world + d] - K, 0);
-            d++;
-        }
-        const int r = t - first;
-        float* o;
-        if (r < K) {
-            o = blocks + ((size_t)d * K + r) * rw;
-        } else {
-            const int oi = ofirst + r - K;
-            if (oi >= ovf_capacity) {
-                if (threadIdx.x == 0) ovf_flag[0] = 1;
-                continue;
-            }
-            o = ovf + (size_t)oi * rw;
-        }
-        const int p = send_src[t];
-        const int sref = src[p];
-        record_write(o, cap, cn_stride, &pose[p], logw_value, slab_of(sref, map_in, size_in, map_x, size_x, cap),
-                     slab_cn(sref, cn, cn_x, cn_stride));
-    }
-}
-
-/* Receive side: deficit slot d + i takes record recv_rec[i] (records numbered
- * in source-rank order, mig[2 world + s] from source s); record r of source s
- * is slot s * K + r of the fixed blocks, or (overflow != 0) position
- * Σ_{s' < s} max(recv_s' - K, 0) + r - K of the received overflow buffer.  The
- * first slot of each record copies its map into migration slab recv_rec[i] of
- * set X; every slot of the record points at it.  One workgroup per slot at a
- * time, strided over a grid of min(n, 256) (the deficit is read on the device). */
-__global__ void __launch_bounds__(256)
-    k_unpack_blocks(const float* __restrict__ blocks, const float* __restrict__ ovf, int block_records, int overflow,
-                    const int* __restrict__ mig, int world, int rank, const int* __restrict__ recv_rec, int n,
-                    int cap, float* __restrict__ map_x, int* __restrict__ size_x, int* __restrict__ src,
-                    phd_pose* __restrict__ pose, float* __restrict__ logw, double* __restrict__ cn_x,
-                    int cn_stride) {
-    const int d = min(mig[rank], n);
-    const int K = block_records;
-    const size_t rw = record_words(cap, cn_stride);
-    // receiving slots d + i, i in [0, n - d), strided over the grid (a grid of
-    // min(n, 256) workgroups: a step that moves nothing costs one short wave each)
-    for (int i = blockIdx.x; d + i < n; i += gridDim.x) {
-        const int rho = recv_rec[i];
-        int s = 0, first = 0, ofirst = 0;
-        while (s < world - 1 && rho >= first + mig[2 * world + s]) {
-            first += mig[2 * world + s];
-            ofirst += max(mig[2 * world + s] - K, 0);
-            s++;
-        }
-        const int r = rho - first;
-        if ((r >= K) != (overflow != 0)) continue;  // the other pass's record
-        const float* o = r < K ? blocks + ((size_t)s * K + r) * rw : ovf + (size_t)(ofirst + r - K) * rw;
-        record_read(o, cap, cn_stride, d + i, rho, !(i > 0 && recv_rec[i - 1] == rho), map_x, size_x, src, pose, logw,
-                    cn_x);
     }
 }
 

@@ -27,9 +27,9 @@
  *        order; one lane sums them in that order in double, so the moments
  *        equal the oracle's bit for bit; static out-of-range components are
  *        appended.
- * k_predict_dynamic_x, k_pack_mx .. k_unpack_blocks_mx: the sharded step's
- *   share — the prediction of the dynamic migration set X in place, and the
- *   migration records that carry the dynamic map (phd_slab.h).
+ * k_predict_dynamic_x: the sharded step's share — the prediction of the
+ *   dynamic migration set X in place (the migration records that carry the
+ *   dynamic map: phd_records.hip).
  * The arithmetic is include/phd_mixed.h (the oracle restates it on its own in
  * oracle/mixed_ref.h; both are held to tests/mixed_ref64.py).  This is a
  * correctness-first form: no benchmark config of the reference uses the mixed
@@ -45,7 +45,6 @@
 #include <vector>
 
 #include "phd_detmath.h"
-#include "phd_kernels.h" /* MIG_*: the plan's counts the block forms read */
 #include "phd_mixed_k.h"
 
 namespace phd {
@@ -465,179 +464,6 @@ __global__ void __launch_bounds__(256) k_predict_dynamic_x(const int* slots, con
         for (int i = 0; i < 4; i++) d[(1 + i) * dcap + k] = mo[i];
         for (int i = 0; i < 16; i++) d[(5 + i) * dcap + k] = po[i];
     }
-}
-
-/* ---- migration records of a mixed context (phd_slab.h) ---- */
-
-/* The first sz components of the PHD_DYN_FIELDS rows of a dynamic map (row
- * stride dcap on both sides), by one workgroup: whole quads of a row as
- * float4 when both sides and the stride are 16-byte aligned, the up to three
- * components left of each row (or everything, unaligned) one float at a time.
- * Consecutive threads take consecutive quads / components of a row. */
-__device__ __forceinline__ void mx_copy_rows(float* __restrict__ d, const float* __restrict__ s, int dcap, int sz) {
-    const bool vec = (dcap & 3) == 0 && ((((uintptr_t)d) | ((uintptr_t)s)) & 15) == 0;
-    const int nq = vec ? sz >> 2 : 0;
-    for (int i = threadIdx.x; i < PHD_DYN_FIELDS * nq; i += blockDim.x) {
-        const int f = i / nq, q = i - f * nq;
-        ((float4*)(d + (size_t)f * dcap))[q] = ((const float4*)(s + (size_t)f * dcap))[q];
-    }
-    const int t0 = nq << 2, nt = sz - t0;
-    for (int i = threadIdx.x; i < PHD_DYN_FIELDS * nt; i += blockDim.x) {
-        const int f = i / nt, k = t0 + (i - f * nt);
-        d[(size_t)f * dcap + k] = s[(size_t)f * dcap + k];
-    }
-}
-
-struct MxRec {
-    size_t rw, doff;  // words of a record, of its dynamic part's offset
-};
-__device__ __forceinline__ MxRec mx_rec(const MixedStore& S) {
-    return MxRec{record_words_mixed(S.cap, 0, S.dcap), record_dyn_offset(S.cap, 0)};
-}
-
-/* One workgroup writes particle p's record at o: the static record
- * (record_write) and then its dynamic map. */
-__device__ __forceinline__ void mx_record_write(const MixedStore& S, const MxRec& R, float* o, int p, float logw) {
-    const int sref = S.src[p];
-    record_write(o, S.cap, 0, &S.pose[p], logw, slab_of(sref, S.map_in, S.size_in, S.map_x, S.size_x, S.cap), nullptr);
-    const int dsz = min(max(slab_size(sref, S.dsize_in, S.dsize_x), 0), S.dcap);
-    float* od = o + R.doff;
-    if (threadIdx.x < PHD_REC_DYN_HEAD) ((int*)od)[threadIdx.x] = threadIdx.x == 0 ? dsz : 0;
-    mx_copy_rows(od + PHD_REC_DYN_HEAD, dyn_slab_map(sref, S.dmap_in, (const float*)S.dmap_x, S.dcap), S.dcap, dsz);
-}
-
-/* One workgroup reads the record at o into particle p, which then refers to
- * slab xs of the sets X; with_map: it also fills that slab of both sets. */
-__device__ __forceinline__ void mx_record_read(const MixedStore& S, const MxRec& R, const float* o, int p, int xs,
-                                               bool with_map) {
-    record_read(o, S.cap, 0, p, xs, with_map, S.map_x, S.size_x, S.src, S.pose, S.logw, nullptr);
-    if (!with_map) return;
-    const float* od = o + R.doff;
-    const int dsz = min(max(((const int*)od)[0], 0), S.dcap);  // a record never carries more than dcap
-    if (threadIdx.x == 0) S.dsize_x[xs] = dsz;
-    mx_copy_rows(S.dmap_x + (size_t)xs * PHD_DYN_FIELDS * S.dcap, od + PHD_REC_DYN_HEAD, S.dcap, dsz);
-}
-
-/* k_pack's form (phd_kernels.hip): the grid strides over the records */
-__global__ void __launch_bounds__(256) k_pack_mx(MixedStore S, const int* __restrict__ dcount,
-                                                 const int* __restrict__ src_idx, int count, int logw_set,
-                                                 float logw_value, float* __restrict__ rec) {
-    if (dcount) count = min(*dcount, count);
-    const MxRec R = mx_rec(S);
-    for (int r = blockIdx.x; r < count; r += gridDim.x) {
-        const int p = src_idx[r];
-        mx_record_write(S, R, rec + (size_t)r * R.rw, p, logw_set ? logw_value : S.logw[p]);
-    }
-}
-
-/* k_unpack's form: record r into slab r of the sets X, particle dst_idx[r] points at it */
-__global__ void __launch_bounds__(256) k_unpack_mx(MixedStore S, const float* __restrict__ rec,
-                                                   const int* __restrict__ dst_idx, int count) {
-    const int r = blockIdx.x;
-    if (r >= count) return;
-    const MxRec R = mx_rec(S);
-    mx_record_read(S, R, rec + (size_t)r * R.rw, dst_idx[r], r, true);
-}
-
-/* k_unpack_slots' form: slot first_slot + i takes record slot_rec[i]; the first
- * slot of a record copies its maps, every slot of the record points at them */
-__global__ void __launch_bounds__(256) k_unpack_slots_mx(MixedStore S, const float* __restrict__ rec,
-                                                         const int* __restrict__ slot_rec, int nslots,
-                                                         int first_slot) {
-    const int i = blockIdx.x;
-    if (i >= nslots) return;
-    const int r = slot_rec[i];
-    const MxRec R = mx_rec(S);
-    mx_record_read(S, R, rec + (size_t)r * R.rw, first_slot + i, r, !(i > 0 && slot_rec[i - 1] == r));
-}
-
-/* k_pack_blocks' form: the same record numbering, block slots and overflow positions */
-__global__ void __launch_bounds__(256) k_pack_blocks_mx(MixedStore S, const int* __restrict__ mig, int world,
-                                                        const int* __restrict__ send_src, int block_records,
-                                                        int ovf_capacity, float logw_value,
-                                                        float* __restrict__ blocks, float* __restrict__ ovf,
-                                                        int* __restrict__ ovf_flag) {
-    const int count = mig[3 * world + MIG_SENT];
-    const MxRec R = mx_rec(S);
-    const int K = block_records;
-    for (int t = blockIdx.x; t < count; t += gridDim.x) {
-        int d = 0, first = 0, ofirst = 0;
-        while (d < world - 1 && t >= first + mig[world + d]) {
-            first += mig[world + d];
-            ofirst += max(mig[world + d] - K, 0);
-            d++;
-        }
-        const int r = t - first;
-        float* o;
-        if (r < K) {
-            o = blocks + ((size_t)d * K + r) * R.rw;
-        } else {
-            const int oi = ofirst + r - K;
-            if (oi >= ovf_capacity) {
-                if (threadIdx.x == 0) ovf_flag[0] = 1;
-                continue;
-            }
-            o = ovf + (size_t)oi * R.rw;
-        }
-        mx_record_write(S, R, o, send_src[t], logw_value);
-    }
-}
-
-/* k_unpack_blocks' form: deficit slot d + i takes record recv_rec[i], from the
- * fixed blocks or (overflow != 0) from the received overflow buffer */
-__global__ void __launch_bounds__(256) k_unpack_blocks_mx(MixedStore S, const float* __restrict__ blocks,
-                                                          const float* __restrict__ ovf, int block_records,
-                                                          int overflow, const int* __restrict__ mig, int world,
-                                                          int rank, const int* __restrict__ recv_rec, int n) {
-    const int d = min(mig[rank], n);
-    const int K = block_records;
-    const MxRec R = mx_rec(S);
-    for (int i = blockIdx.x; d + i < n; i += gridDim.x) {
-        const int rho = recv_rec[i];
-        int s = 0, first = 0, ofirst = 0;
-        while (s < world - 1 && rho >= first + mig[2 * world + s]) {
-            first += mig[2 * world + s];
-            ofirst += max(mig[2 * world + s] - K, 0);
-            s++;
-        }
-        const int r = rho - first;
-        if ((r >= K) != (overflow != 0)) continue;  // the other pass's record
-        const float* o = r < K ? blocks + ((size_t)s * K + r) * R.rw : ovf + (size_t)(ofirst + r - K) * R.rw;
-        mx_record_read(S, R, o, d + i, rho, !(i > 0 && recv_rec[i - 1] == rho));
-    }
-}
-
-hipError_t mixed_launch_pack(const MixedStore& S, int grid, const int* dcount, const int* src_idx, int count,
-                             int logw_set, float logw_value, float* rec, hipStream_t s) {
-    hipLaunchKernelGGL(k_pack_mx, dim3(grid), dim3(256), 0, s, S, dcount, src_idx, count, logw_set, logw_value, rec);
-    return hipGetLastError();
-}
-
-hipError_t mixed_launch_unpack(const MixedStore& S, const float* rec, const int* dst_idx, int count, hipStream_t s) {
-    hipLaunchKernelGGL(k_unpack_mx, dim3(count), dim3(256), 0, s, S, rec, dst_idx, count);
-    return hipGetLastError();
-}
-
-hipError_t mixed_launch_unpack_slots(const MixedStore& S, const float* rec, const int* slot_rec, int nslots,
-                                     int first_slot, hipStream_t s) {
-    hipLaunchKernelGGL(k_unpack_slots_mx, dim3(nslots), dim3(256), 0, s, S, rec, slot_rec, nslots, first_slot);
-    return hipGetLastError();
-}
-
-hipError_t mixed_launch_pack_blocks(const MixedStore& S, int grid, const int* mig, int world, const int* send_src,
-                                    int block_records, int ovf_capacity, float logw_value, float* blocks, float* ovf,
-                                    int* ovf_flag, hipStream_t s) {
-    hipLaunchKernelGGL(k_pack_blocks_mx, dim3(grid), dim3(256), 0, s, S, mig, world, send_src, block_records,
-                       ovf_capacity, logw_value, blocks, ovf, ovf_flag);
-    return hipGetLastError();
-}
-
-hipError_t mixed_launch_unpack_blocks(const MixedStore& S, int grid, const float* blocks, const float* ovf,
-                                      int block_records, int overflow, const int* mig, int world, int rank,
-                                      const int* recv_rec, int n, hipStream_t s) {
-    hipLaunchKernelGGL(k_unpack_blocks_mx, dim3(grid), dim3(256), 0, s, S, blocks, ovf, block_records, overflow, mig,
-                       world, rank, recv_rec, n);
-    return hipGetLastError();
 }
 
 size_t mixed_lds_bytes(int cap, int dcap, int Mcap, int Kcap) {

@@ -79,37 +79,6 @@ hipError_t mixed_launch_predict_x(const int* slots, int count, const int* src, i
                                   const int* dsize_x, const phd_mx_cfg& c, hipStream_t s);
 hipError_t mixed_set_lds_limit();
 
-/* ---- migration records of a mixed context (phd_slab.h: record_words_mixed) ----
- * The forms of phd_kernels.hip's k_pack / k_unpack / k_unpack_slots /
- * k_pack_blocks / k_unpack_blocks with the same arguments and the same record
- * numbering, for records that carry the dynamic map after the static one; one
- * workgroup per record at a time, the rows copied as 16-byte vectors where the
- * alignment allows it, the first dsize components of each row only. */
-struct MixedStore {
-    int cap, dcap;
-    int* src;
-    const float* map_in;   // current static set
-    const int* size_in;
-    float* map_x;          // static set X
-    int* size_x;
-    const float* dmap_in;  // current dynamic set
-    const int* dsize_in;
-    float* dmap_x;         // dynamic set X
-    int* dsize_x;
-    phd_pose* pose;
-    float* logw;
-};
-hipError_t mixed_launch_pack(const MixedStore& S, int grid, const int* dcount, const int* src_idx, int count,
-                             int logw_set, float logw_value, float* rec, hipStream_t s);
-hipError_t mixed_launch_unpack(const MixedStore& S, const float* rec, const int* dst_idx, int count, hipStream_t s);
-hipError_t mixed_launch_unpack_slots(const MixedStore& S, const float* rec, const int* slot_rec, int nslots,
-                                     int first_slot, hipStream_t s);
-hipError_t mixed_launch_pack_blocks(const MixedStore& S, int grid, const int* mig, int world, const int* send_src,
-                                    int block_records, int ovf_capacity, float logw_value, float* blocks, float* ovf,
-                                    int* ovf_flag, hipStream_t s);
-hipError_t mixed_launch_unpack_blocks(const MixedStore& S, int grid, const float* blocks, const float* ovf,
-                                      int block_records, int overflow, const int* mig, int world, int rank,
-                                      const int* recv_rec, int n, hipStream_t s);
 /* EAP map of the dynamic maps of n particles (exp_map_dynamic): the component
  * count (nothing copied when out is NULL or too small), -1 on a HIP error;
  * d_dmap_x / d_dsize_x: the dynamic set X (NULL: no reference names it) */

@@ -91,8 +91,8 @@ def overflow_slices(send_records, recv_records, block_records, record_bytes):
 
     The sender's overflow buffer holds, per destination d in rank order, its
     records block_records .. send_records[d]-1; the receiver's holds, per source
-    s in rank order, records block_records .. recv_records[s]-1 (the layout of
-    k_pack_blocks / k_unpack_blocks).  Returns ([(d, lo, hi)], [(s, lo, hi)]) in
+    s in rank order, records block_records .. recv_records[s]-1 (record_slot of
+    csrc/phd_records.hip, which the block pack and unpack share).  Returns ([(d, lo, hi)], [(s, lo, hi)]) in
     bytes; both sides derive the same pairs from the same global plan.
     """
     K = block_records

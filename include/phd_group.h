@@ -97,8 +97,8 @@ int phd_group_synchronize(phd_group* g);
 const char* phd_group_last_error(void);
 
 /* Host-side transport plan of the records beyond the fixed blocks (the layout
- * of k_pack_blocks / k_unpack_blocks): the sender's overflow buffer holds, per
- * destination d in rank order, its records block_records .. send_records[d]-1;
+ * of the block pack and unpack, record_slot of phd_records.hip): the sender's
+ * overflow buffer holds, per destination d in rank order, its records block_records .. send_records[d]-1;
  * the receiver's, per source s in rank order, records block_records ..
  * recv_records[s]-1.  Writes (peer, byte offset, byte count) triples — at most
  * world each — and their numbers.  Pure host arithmetic (no device). */

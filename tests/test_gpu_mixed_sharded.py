@@ -48,7 +48,7 @@ def _filter(cfg, n, dcap=DCAP, seed=S):
 @pytest.mark.parametrize("cap,cn,dcap", [(128, 0, 64), (128, 0, 0), (16, 9, 0), (5, 0, 3), (6, 0, 64), (128, 0, 1),
                                          (7, 3, 5)])
 def test_record_bytes_follow_the_documented_layout(built, cap, cn, dcap):
-    """The record-size arithmetic (record_words_mixed, phd_slab.h, through
+    """The record-size arithmetic (record_words_mixed, phd_records.h, through
     phd_record_layout_bytes; no device): the static / CPHD record is
     4 * (8 + 7 cap + 2 cn) bytes as it always was; with a dynamic capacity that
     is padded to 16 bytes, then [dsize | 3 reserved | 21 * dcap floats], padded
