@@ -1,6 +1,7 @@
 /*
  * phd_capi_estimate.hip — estimates read from the store: expected pose, the
- * EAP expected map (static, dynamic, sharded blocks), cardinalities, LSE parts.
+ * EAP expected map (static, dynamic, the sharded blocks of both), cardinalities,
+ * LSE parts.
  */
 #include <hip/hip_runtime.h>
 
@@ -107,8 +108,30 @@ int phd_expected_map_groups(phd_ctx* ctx, int* groups) {
 static int eap_shard_check(phd_ctx* ctx, const char* who) {
     if (!ctx) return fail(PHD_E_ARG, std::string("null ctx in ") + who);
     if (!ctx->cfg_set) return fail(PHD_E_ARG, "phd_set_config first");
-    if (ctx->cfg.featureModel != PHD_FEATURE_STATIC)
-        return fail(PHD_E_UNSUPPORTED, std::string(who) + " with feature_model != 0");
+    // a mixed context's static maps live in the same slab sets and migration set as a
+    // static context's: the pack and the reduce are the same
+    const bool mixed = ctx->cfg.featureModel == PHD_FEATURE_MIXED && ctx->mx.on;
+    if (ctx->cfg.featureModel != PHD_FEATURE_STATIC && !mixed)
+        return fail(PHD_E_UNSUPPORTED, std::string(who) + " with feature_model != 0 (feature_model 2: after "
+                                                          "phd_enable_dynamic only)");
+    return PHD_OK;
+}
+
+/* world blocks of block_bytes each must lie inside the allocation dev_blocks
+ * points into (where the runtime knows it): no header is read past the
+ * caller's buffer */
+static int blocks_fit(const void* dev_blocks, int world, long K_max, size_t block_bytes, const char* who) {
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)dev_blocks) == hipSuccess && base) {
+        const size_t room = size - (size_t)((const char*)dev_blocks - (const char*)base);
+        if ((size_t)world * block_bytes > room)
+            return fail(PHD_E_ARG, std::string(who) + ": " + std::to_string(world) + " blocks of K_max " +
+                                       std::to_string(K_max) + " do not fit the buffer (" + std::to_string(room) +
+                                       " bytes from dev_blocks)");
+    } else {
+        (void)hipGetLastError();
+    }
     return PHD_OK;
 }
 
@@ -153,21 +176,8 @@ int phd_expected_map_blocks(phd_ctx* ctx, const void* dev_blocks, int world, lon
         return fail(PHD_E_ARG, "bad arguments to phd_expected_map_blocks (world in [1, 1024], K_max in [0, 2^31 - 1), "
                                "16-byte aligned blocks)");
     if (set_device(ctx)) return PHD_E_HIP;
-    // world blocks of this K_max must lie inside the allocation dev_blocks points into
-    // (where the runtime knows it): no header is read past the caller's buffer
-    {
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)dev_blocks) == hipSuccess && base) {
-            const size_t room = size - (size_t)((const char*)dev_blocks - (const char*)base);
-            if ((size_t)world * eap_block_bytes(K_max) > room)
-                return fail(PHD_E_ARG, "phd_expected_map_blocks: " + std::to_string(world) + " blocks of K_max " +
-                                           std::to_string(K_max) + " do not fit the buffer (" + std::to_string(room) +
-                                           " bytes from dev_blocks)");
-        } else {
-            (void)hipGetLastError();
-        }
-    }
+    rc = blocks_fit(dev_blocks, world, K_max, eap_block_bytes(K_max), "phd_expected_map_blocks");
+    if (rc) return rc;
     std::string err;
     const long nout = eap_run_blocks(&ctx->eap, ctx->stream, dev_blocks, world, ctx->n, K_max, ctx->cfg.minSeparation,
                                      out, out ? out_cap : 0, &ctx->eap_groups, err);
@@ -176,6 +186,72 @@ int phd_expected_map_blocks(phd_ctx* ctx, const void* dev_blocks, int world, lon
     *n_out = nout;
     if (nout > 0 && (!out || nout > out_cap))
         return fail(PHD_E_CAPACITY, "expected map has " + std::to_string(nout) + " components; out_cap too small");
+    return PHD_OK;
+}
+
+/* ---- the EAP map of the dynamic maps of a sharded mixed filter (phd_mixed.hip: blocks) ---- */
+
+static int eap_dyn_check(phd_ctx* ctx, const char* who) {
+    if (!ctx) return fail(PHD_E_ARG, std::string("null ctx in ") + who);
+    if (!ctx->cfg_set) return fail(PHD_E_ARG, std::string(who) + ": phd_set_config first");
+    if (!ctx->mx.on) return fail(PHD_E_ARG, std::string(who) + ": phd_enable_dynamic not called");
+    return PHD_OK;
+}
+
+int phd_eap_dyn_shard_count(phd_ctx* ctx, long* K_local) {
+    int rc = eap_dyn_check(ctx, "phd_eap_dyn_shard_count");
+    if (rc) return rc;
+    if (!K_local) return fail(PHD_E_ARG, "null argument");
+    if (set_device(ctx)) return PHD_E_HIP;
+    std::string err;
+    const long k = eap4_shard_count(ctx->stream, ctx->st.d_src, ctx->mx.d_dsize[ctx->mx.dcur],
+                                    ctx->mx.d_dsize_x, ctx->n, ctx->mx.dcap, err);
+    if (k < 0) return fail(PHD_E_HIP, "phd_eap_dyn_shard_count: " + err);
+    *K_local = k;
+    return PHD_OK;
+}
+
+int phd_eap_dyn_shard_block_bytes(long K_max, size_t* bytes) {
+    if (K_max < 0 || !bytes) return fail(PHD_E_ARG, "bad arguments to phd_eap_dyn_shard_block_bytes");
+    *bytes = eap4_block_bytes(K_max);
+    return PHD_OK;
+}
+
+int phd_eap_dyn_shard_pack(phd_ctx* ctx, long K_max, void* dev_block) {
+    int rc = eap_dyn_check(ctx, "phd_eap_dyn_shard_pack");
+    if (rc) return rc;
+    if (K_max < 0 || K_max >= (1L << 31) - 1 || !dev_block || ((uintptr_t)dev_block & 15))
+        return fail(PHD_E_ARG,
+                    "bad arguments to phd_eap_dyn_shard_pack (K_max in [0, 2^31 - 1), a 16-byte aligned block)");
+    if (set_device(ctx)) return PHD_E_HIP;
+    std::string err;
+    rc = eap4_shard_pack(&ctx->eap4, ctx->stream, ctx->st.d_src, ctx->mx.d_dmap[ctx->mx.dcur],
+                         ctx->mx.d_dsize[ctx->mx.dcur], ctx->mx.d_dmap_x, ctx->mx.d_dsize_x, ctx->st.d_logw, ctx->n,
+                         ctx->mx.dcap, K_max, dev_block, err);
+    if (rc == -2) return fail(PHD_E_ARG, "phd_eap_dyn_shard_pack: " + err);
+    if (rc) return fail(PHD_E_HIP, "phd_eap_dyn_shard_pack: " + err);
+    return PHD_OK;
+}
+
+int phd_expected_map_dynamic_blocks(phd_ctx* ctx, const void* dev_blocks, int world, long K_max, phd_gaussian4d* out,
+                                    long out_cap, long* n_out) {
+    int rc = eap_dyn_check(ctx, "phd_expected_map_dynamic_blocks");
+    if (rc) return rc;
+    if (!n_out || !dev_blocks || ((uintptr_t)dev_blocks & 15) || world < 1 || world > EAP_MAX_WORLD || K_max < 0 ||
+        K_max >= (1L << 31) - 1)
+        return fail(PHD_E_ARG, "bad arguments to phd_expected_map_dynamic_blocks (world in [1, 1024], K_max in "
+                               "[0, 2^31 - 1), 16-byte aligned blocks)");
+    if (set_device(ctx)) return PHD_E_HIP;
+    rc = blocks_fit(dev_blocks, world, K_max, eap4_block_bytes(K_max), "phd_expected_map_dynamic_blocks");
+    if (rc) return rc;
+    std::string err;
+    const long nout = mixed_expected_map_dynamic_blocks(&ctx->eap4, ctx->stream, dev_blocks, world, ctx->n, K_max,
+                                                        ctx->cfg.minSeparation, out, out ? out_cap : 0, err);
+    if (nout == -2) return fail(PHD_E_ARG, "phd_expected_map_dynamic_blocks: " + err);
+    if (nout < 0) return fail(PHD_E_HIP, "dynamic expected map: " + err);
+    *n_out = nout;
+    if (nout > 0 && (!out || nout > out_cap))
+        return fail(PHD_E_CAPACITY, "dynamic expected map has " + std::to_string(nout) + " components; out_cap too small");
     return PHD_OK;
 }
 

@@ -272,12 +272,14 @@ struct phd_ctx {
     phd::DevBuf<unsigned long long> d_stamps;  // diagnostic builds (PHD_STAMPS)
     phd::EapScratch* eap = nullptr;  // expected-map scratch (phd_eap.hip), allocated on first use
     int eap_groups = 0;
+    phd::Eap4Scratch* eap4 = nullptr;  // the dynamic maps' blocks form (phd_mixed.hip), allocated on first use
 
     /* waits for the context stream, then the members release (the stream last) */
     ~phd_ctx() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
         if (eap) phd::eap_free(eap);
+        if (eap4) phd::eap4_free(eap4);
     }
 };
 

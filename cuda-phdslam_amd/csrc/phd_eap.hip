@@ -936,10 +936,11 @@ __global__ void k_eap_block_head(unsigned int* __restrict__ head, unsigned int K
 /* The gathered headers (one workgroup): every header checked (layout word, n,
  * stride, K_r <= K_max; a refused header counts no component), the counts
  * exclusive-scanned into off[world + 1] (rank order), Λ the maximum and the
- * non-finite flag the OR over the headers.  sum: EAP_HS_* words. */
+ * non-finite flag the OR over the headers (both words are zero in the dynamic
+ * maps' "EAP4" headers, whose reduce reads neither).  sum: EAP_HS_* words. */
 __global__ void __launch_bounds__(256)
-    k_eap_block_heads(const unsigned int* __restrict__ blocks, size_t stride_words, int world, unsigned int n,
-                      unsigned int K_max, int* __restrict__ off, unsigned int* __restrict__ sum) {
+    k_eap_block_heads(const unsigned int* __restrict__ blocks, size_t stride_words, int world, unsigned int layout,
+                      unsigned int n, unsigned int K_max, int* __restrict__ off, unsigned int* __restrict__ sum) {
     __shared__ unsigned int s_cnt[EAP_MAX_WORLD];
     __shared__ unsigned int s_lam, s_bad, s_refused;
     if (threadIdx.x == 0) {
@@ -952,7 +953,7 @@ __global__ void __launch_bounds__(256)
         const unsigned int* h = blocks + (size_t)r * stride_words;
         const unsigned int kr = h[EAP_BH_COUNT];
         unsigned int why = 0u;
-        if (h[EAP_BH_LAYOUT] != EAP_BLOCK_LAYOUT || h[EAP_BH_KMAX] != K_max) why = EAP_REFUSED_LAYOUT;
+        if (h[EAP_BH_LAYOUT] != layout || h[EAP_BH_KMAX] != K_max) why = EAP_REFUSED_LAYOUT;
         else if (h[EAP_BH_N] != n) why = EAP_REFUSED_N;
         else if (kr > K_max) why = EAP_REFUSED_COUNT;
         s_cnt[r] = why ? 0u : kr;
@@ -979,7 +980,7 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-/* Concatenate: field f (blockIdx.y) of rank r's block (blockIdx.z), K_r floats
+/* Concatenate: field f (blockIdx.y: 7 static, 21 dynamic) of rank r's block (blockIdx.z), K_r floats
  * at stride K_max behind the header, to comp[f K + off[r] ..): coalesced, 16 B
  * per lane where source and destination share their alignment (a scalar head
  * up to the first 16-byte boundary and a scalar tail), else 4 B per lane. */
@@ -1010,9 +1011,30 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-size_t eap_block_bytes(long K_max) {
-    const size_t b = (size_t)EAP_BH_WORDS * 4 + (size_t)28 * (size_t)K_max;
+size_t eap_block_bytes_of(int fields, long K_max) {
+    const size_t b = (size_t)EAP_BH_WORDS * 4 + (size_t)fields * 4 * (size_t)K_max;
     return (b + 15) & ~(size_t)15;
+}
+
+size_t eap_block_bytes(long K_max) { return eap_block_bytes_of(7, K_max); }
+
+void eap_launch_block_heads(hipStream_t st, const void* d_blocks, size_t stride_words, int world, unsigned int layout,
+                            int n, long K_max, int* d_off, unsigned int* d_sum) {
+    hipLaunchKernelGGL(k_eap_block_heads, dim3(1), dim3(256), 0, st, (const unsigned int*)d_blocks, stride_words, world,
+                       layout, (unsigned int)n, (unsigned int)K_max, d_off, d_sum);
+}
+
+void eap_launch_concat(hipStream_t st, const void* d_blocks, size_t stride_words, int fields, int world, long K_max,
+                       const int* d_off, long K, float* comp) {
+    const unsigned int gx = (unsigned int)std::min<long>(std::max<long>((K_max + 1023) / 1024, 1), 4096);
+    hipLaunchKernelGGL(k_eap_concat, dim3(gx, fields, world), dim3(256), 0, st, (const unsigned int*)d_blocks,
+                       stride_words, K_max, d_off, K, comp);
+}
+
+std::string eap_refused_text(unsigned int refused) {
+    static const char* const why[] = {"", "its layout word or stride does not match", "its particle count does not match",
+                                      "its component count exceeds K_max"};
+    return "the block of rank " + std::to_string(refused / 4u) + " is refused: " + why[refused & 3u];
 }
 
 /* Component count of the store (what this rank's block will hold), or -1. */
@@ -1079,15 +1101,12 @@ long eap_run_blocks(EapScratch** sp, hipStream_t st, const void* d_blocks, int w
     int* d_off = S.heads;
     unsigned int* d_sum = (unsigned int*)(S.heads + world + 1);
     const size_t stride_words = eap_block_bytes(K_max) / 4;
-    hipLaunchKernelGGL(k_eap_block_heads, dim3(1), dim3(256), 0, st, (const unsigned int*)d_blocks, stride_words, world,
-                       (unsigned int)n, (unsigned int)K_max, d_off, d_sum);
+    eap_launch_block_heads(st, d_blocks, stride_words, world, EAP_BLOCK_LAYOUT, n, K_max, d_off, d_sum);
     unsigned int sum[EAP_HS_WORDS];
     EAPCHK(hipMemcpyAsync(sum, d_sum, sizeof(sum), hipMemcpyDeviceToHost, st));
     EAPCHK(hipStreamSynchronize(st));
     if (sum[EAP_HS_REFUSED] != 0xffffffffu) {
-        static const char* const why[] = {"", "its layout word or stride does not match", "its particle count does not match",
-                                          "its component count exceeds K_max"};
-        err = "the block of rank " + std::to_string(sum[EAP_HS_REFUSED] / 4u) + " is refused: " + why[sum[EAP_HS_REFUSED] & 3u];
+        err = eap_refused_text(sum[EAP_HS_REFUSED]);
         return -2;
     }
     const unsigned long long total = ((unsigned long long)sum[EAP_HS_TOTAL_HI] << 32) | sum[EAP_HS_TOTAL_LO];
@@ -1101,9 +1120,7 @@ long eap_run_blocks(EapScratch** sp, hipStream_t st, const void* d_blocks, int w
     size_t tmp = 0;
     if (eap_scratch(S, st, K, world, &B, &tmp, err)) return -1;
     EAPCHK(hipMemsetAsync(B.misc, 0, 8 * sizeof(unsigned int), st));
-    const unsigned int gx = (unsigned int)std::min<long>(std::max<long>((K_max + 1023) / 1024, 1), 4096);
-    hipLaunchKernelGGL(k_eap_concat, dim3(gx, 7, world), dim3(256), 0, st, (const unsigned int*)d_blocks, stride_words,
-                       K_max, d_off, K, B.comp);
+    eap_launch_concat(st, d_blocks, stride_words, 7, world, K_max, d_off, K, B.comp);
     EAPCHK(hipGetLastError());
     return eap_reduce(S, st, B, tmp, K, sum[EAP_HS_LAM], sum[EAP_HS_BAD], T, out, out_cap, n_groups, err);
 }

@@ -52,9 +52,10 @@ struct Rank {
     unsigned char* ovf_recv = nullptr;     // n * record_bytes
     unsigned char* tr_block = nullptr;     // trace_bytes (phd_group_trace_enable)
     unsigned char* tr_blocks = nullptr;    // world * trace_bytes
-    long long* eap_cnt = nullptr;          // world + 1: the ranks' component counts | this rank's (phd_group_expected_map)
-    unsigned char* eap_block = nullptr;    // eap_bytes
-    unsigned char* eap_blocks = nullptr;   // world * eap_bytes
+    // the expected maps' buffers (eap_gather): [0] the static map's, [1] the dynamic maps'
+    long long* eap_cnt[2] = {nullptr, nullptr};         // world + 1: the ranks' component counts | this rank's
+    unsigned char* eap_block[2] = {nullptr, nullptr};   // eap_bytes
+    unsigned char* eap_blocks[2] = {nullptr, nullptr};  // world * eap_bytes
     std::vector<long long> sends, recvs;   // overflow (peer, offset, bytes) triples of the open plan
 };
 
@@ -65,7 +66,7 @@ struct phd_group {
     size_t rec = 0;
     int ovf_capacity = 0;
     size_t trace_bytes = 0;  // a rank's trace block (0: the trace is off)
-    size_t eap_bytes = 0;    // room of a rank's expected-map block (grown on demand)
+    size_t eap_bytes[2] = {0, 0};  // room of a rank's expected-map block, static | dynamic (grown on demand)
     uint64_t seed = 0;
     float new_logw = 0.f;
     bool open = false;
@@ -130,7 +131,7 @@ static void free_rank(Rank& k) {
     (void)hipSetDevice(k.device);
     void* p[] = {k.w_local, k.w_all, k.parents, k.keep_src, k.send_src, k.recv_rec,
                  k.send_blocks, k.recv_blocks, k.ovf_send, k.ovf_recv, k.tr_block, k.tr_blocks,
-                 k.eap_cnt,  k.eap_block, k.eap_blocks};
+                 k.eap_cnt[0], k.eap_block[0], k.eap_blocks[0], k.eap_cnt[1], k.eap_block[1], k.eap_blocks[1]};
     for (void* q : p)
         if (q) (void)hipFree(q);
     if (k.comm) ncclCommDestroy(k.comm);
@@ -435,30 +436,38 @@ int phd_group_flush(phd_group* g) {
     return phd_group_synchronize(g);
 }
 
-int phd_group_expected_map(phd_group* g, phd_gaussian2d* out, long out_cap, long* n_out) {
-    if (!g || !n_out) return gfail(PHD_E_ARG, "bad arguments to phd_group_expected_map");
+}  // extern "C"
+
+/* The first two phases of an expected map of the whole filter, for the static
+ * map (dyn 0) or the dynamic maps (dyn 1): the stores settled, every rank's
+ * component count all-gathered (K_max their maximum, total their sum), the
+ * blocks packed and all-gathered in rank order into eap_blocks[dyn]. */
+static int eap_gather(phd_group* g, int dyn, long* K_max_out, long* total_out) {
     const int W = g->world;
     int rc = phd_group_flush(g);  // the stores are final
     if (rc) return rc;
     // 1. every rank's component count, all-gathered; K_max their maximum
     for (Rank& k : g->r) {
         long cnt = 0;
-        PHDCHK(phd_eap_shard_count(k.ctx, &cnt));
+        if (dyn)
+            PHDCHK(phd_eap_dyn_shard_count(k.ctx, &cnt));
+        else
+            PHDCHK(phd_eap_shard_count(k.ctx, &cnt));
         HIPCHKG(hipSetDevice(k.device));
-        if (!k.eap_cnt) HIPCHKG(hipMalloc((void**)&k.eap_cnt, (size_t)(W + 1) * sizeof(long long)));
+        if (!k.eap_cnt[dyn]) HIPCHKG(hipMalloc((void**)&k.eap_cnt[dyn], (size_t)(W + 1) * sizeof(long long)));
         const long long c = cnt;
-        HIPCHKG(hipMemcpyAsync(k.eap_cnt + W, &c, sizeof(c), hipMemcpyHostToDevice, k.st));
+        HIPCHKG(hipMemcpyAsync(k.eap_cnt[dyn] + W, &c, sizeof(c), hipMemcpyHostToDevice, k.st));
         HIPCHKG(hipStreamSynchronize(k.st));  // (c leaves scope)
     }
     NCCLCHK(ncclGroupStart());
-    for (Rank& k : g->r) NCCLCHK(ncclAllGather(k.eap_cnt + W, k.eap_cnt, 1, ncclInt64, k.comm, k.st));
+    for (Rank& k : g->r) NCCLCHK(ncclAllGather(k.eap_cnt[dyn] + W, k.eap_cnt[dyn], 1, ncclInt64, k.comm, k.st));
     NCCLCHK(ncclGroupEnd());
     std::vector<long long> cnts(W);
     long K_max = 0, total = 0;
     for (size_t r = 0; r < g->r.size(); r++) {
         Rank& k = g->r[r];
         HIPCHKG(hipSetDevice(k.device));
-        HIPCHKG(hipMemcpyAsync(cnts.data(), k.eap_cnt, (size_t)W * sizeof(long long), hipMemcpyDeviceToHost, k.st));
+        HIPCHKG(hipMemcpyAsync(cnts.data(), k.eap_cnt[dyn], (size_t)W * sizeof(long long), hipMemcpyDeviceToHost, k.st));
         HIPCHKG(hipStreamSynchronize(k.st));
         if (r) continue;  // (identical on every rank)
         for (int d = 0; d < W; d++) {
@@ -468,43 +477,92 @@ int phd_group_expected_map(phd_group* g, phd_gaussian2d* out, long out_cap, long
     }
     // 2. the blocks: packed, all-gathered in rank order
     size_t bytes = 0;
-    PHDCHK(phd_eap_shard_block_bytes(K_max, &bytes));
-    if (bytes > g->eap_bytes) {
+    if (dyn)
+        PHDCHK(phd_eap_dyn_shard_block_bytes(K_max, &bytes));
+    else
+        PHDCHK(phd_eap_shard_block_bytes(K_max, &bytes));
+    if (bytes > g->eap_bytes[dyn]) {
         for (Rank& k : g->r) {
             HIPCHKG(hipSetDevice(k.device));
-            if (k.eap_block) (void)hipFree(k.eap_block);
-            if (k.eap_blocks) (void)hipFree(k.eap_blocks);
-            k.eap_block = k.eap_blocks = nullptr;
+            if (k.eap_block[dyn]) (void)hipFree(k.eap_block[dyn]);
+            if (k.eap_blocks[dyn]) (void)hipFree(k.eap_blocks[dyn]);
+            k.eap_block[dyn] = k.eap_blocks[dyn] = nullptr;
         }
-        g->eap_bytes = 0;
+        g->eap_bytes[dyn] = 0;
         for (Rank& k : g->r) {
             HIPCHKG(hipSetDevice(k.device));
-            HIPCHKG(hipMalloc((void**)&k.eap_block, bytes));
-            HIPCHKG(hipMalloc((void**)&k.eap_blocks, bytes * W));
+            HIPCHKG(hipMalloc((void**)&k.eap_block[dyn], bytes));
+            HIPCHKG(hipMalloc((void**)&k.eap_blocks[dyn], bytes * W));
         }
-        g->eap_bytes = bytes;
+        g->eap_bytes[dyn] = bytes;
     }
-    for (Rank& k : g->r) PHDCHK(phd_eap_shard_pack(k.ctx, K_max, k.eap_block));
+    for (Rank& k : g->r) {
+        if (dyn)
+            PHDCHK(phd_eap_dyn_shard_pack(k.ctx, K_max, k.eap_block[dyn]));
+        else
+            PHDCHK(phd_eap_shard_pack(k.ctx, K_max, k.eap_block[dyn]));
+    }
     NCCLCHK(ncclGroupStart());
-    for (Rank& k : g->r) NCCLCHK(ncclAllGather(k.eap_block, k.eap_blocks, bytes, ncclUint8, k.comm, k.st));
+    for (Rank& k : g->r)
+        NCCLCHK(ncclAllGather(k.eap_block[dyn], k.eap_blocks[dyn], bytes, ncclUint8, k.comm, k.st));
     NCCLCHK(ncclGroupEnd());
-    // 3. every rank reduces the whole set; rank 0's copy is returned
-    std::vector<phd_gaussian2d> other;
+    *K_max_out = K_max;
+    *total_out = total;
+    return PHD_OK;
+}
+
+/* The third phase: every rank of this process reduces the whole set with
+ * reduce(ctx, blocks, K_max, out, out_cap, n_out); rank 0's copy is returned. */
+template <class G, class Reduce>
+static int eap_reduce_all(phd_group* g, int dyn, long K_max, long total, G* out, long out_cap, long* n_out,
+                          Reduce reduce, const char* who) {
+    std::vector<G> other;
     long n0 = 0;
     for (size_t r = 0; r < g->r.size(); r++) {
         Rank& k = g->r[r];
         long nr = 0;
         if (r == 0) {
-            rc = phd_expected_map_blocks(k.ctx, k.eap_blocks, W, K_max, out, out_cap, &nr);
+            const int rc = reduce(k.ctx, k.eap_blocks[dyn], K_max, out, out_cap, &nr);
             *n_out = n0 = nr;
-            if (rc != PHD_OK) return gfail(rc, std::string("phd_expected_map_blocks: ") + phd_last_error());
+            if (rc != PHD_OK) return gfail(rc, std::string(who) + ": " + phd_last_error());
         } else {
             other.resize((size_t)(total > 0 ? total : 1));
-            PHDCHK(phd_expected_map_blocks(k.ctx, k.eap_blocks, W, K_max, other.data(), total, &nr));
-            if (nr != n0) return gfail(PHD_E_HIP, "phd_group_expected_map: the ranks' maps differ in size");
+            const int rc = reduce(k.ctx, k.eap_blocks[dyn], K_max, other.data(), total, &nr);
+            if (rc != PHD_OK) return gfail(rc, std::string(who) + ": " + phd_last_error());
+            if (nr != n0) return gfail(PHD_E_HIP, std::string(who) + ": the ranks' maps differ in size");
         }
     }
     return PHD_OK;
+}
+
+extern "C" {
+
+int phd_group_expected_map(phd_group* g, phd_gaussian2d* out, long out_cap, long* n_out) {
+    if (!g || !n_out) return gfail(PHD_E_ARG, "bad arguments to phd_group_expected_map");
+    const int W = g->world;
+    long K_max = 0, total = 0;
+    const int rc = eap_gather(g, 0, &K_max, &total);
+    if (rc) return rc;
+    return eap_reduce_all(
+        g, 0, K_max, total, out, out_cap, n_out,
+        [W](phd_ctx* c, const void* blocks, long km, phd_gaussian2d* o, long cap, long* n) {
+            return phd_expected_map_blocks(c, blocks, W, km, o, cap, n);
+        },
+        "phd_expected_map_blocks");
+}
+
+int phd_group_expected_map_dynamic(phd_group* g, phd_gaussian4d* out, long out_cap, long* n_out) {
+    if (!g || !n_out) return gfail(PHD_E_ARG, "bad arguments to phd_group_expected_map_dynamic");
+    const int W = g->world;
+    long K_max = 0, total = 0;
+    const int rc = eap_gather(g, 1, &K_max, &total);
+    if (rc) return rc;
+    return eap_reduce_all(
+        g, 1, K_max, total, out, out_cap, n_out,
+        [W](phd_ctx* c, const void* blocks, long km, phd_gaussian4d* o, long cap, long* n) {
+            return phd_expected_map_dynamic_blocks(c, blocks, W, km, o, cap, n);
+        },
+        "phd_expected_map_dynamic_blocks");
 }
 
 int phd_group_synchronize(phd_group* g) {

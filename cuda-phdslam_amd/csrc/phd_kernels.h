@@ -544,6 +544,7 @@ long eap_run(EapScratch** sp, hipStream_t st, const int* d_src, const float* d_m
              phd_gaussian2d* out, long out_cap, int* n_groups, std::string& err);
 /* the sharded form: a rank's block (layout: include/phd_capi.h) and the reduce of the gathered blocks */
 #define EAP_BLOCK_LAYOUT 0x31504145u /* "EAP1": 64-byte header, 7 float fields of stride K_max */
+#define EAP4_BLOCK_LAYOUT 0x34504145u /* "EAP4": the dynamic maps' block (phd_mixed.hip), 21 float fields */
 #define EAP_BH_WORDS 16   /* header words */
 #define EAP_BH_LAYOUT 0
 #define EAP_BH_COUNT 1    /* K_r */
@@ -569,5 +570,17 @@ int eap_shard_pack(EapScratch** sp, hipStream_t st, const int* d_src, const floa
                    void* d_block, std::string& err);
 long eap_run_blocks(EapScratch** sp, hipStream_t st, const void* d_blocks, int world, int n, long K_max, float T,
                     phd_gaussian2d* out, long out_cap, int* n_groups, std::string& err);
+/* What the static and the dynamic (phd_mixed.hip) blocks forms share: the block
+ * is a header of EAP_BH_WORDS words and `fields` float fields of stride K_max,
+ * rounded up to 16 bytes.  eap_launch_block_heads checks the `world` gathered
+ * headers against `layout`, n and K_max and scans the counts into off[world + 1]
+ * (sum: EAP_HS_WORDS words); eap_launch_concat writes field f of rank r's block
+ * to comp[f K + off[r] ..); eap_refused_text words EAP_HS_REFUSED. */
+size_t eap_block_bytes_of(int fields, long K_max);
+void eap_launch_block_heads(hipStream_t st, const void* d_blocks, size_t stride_words, int world, unsigned int layout,
+                            int n, long K_max, int* d_off, unsigned int* d_sum);
+void eap_launch_concat(hipStream_t st, const void* d_blocks, size_t stride_words, int fields, int world, long K_max,
+                       const int* d_off, long K, float* comp);
+std::string eap_refused_text(unsigned int refused);
 
 }  // namespace phd

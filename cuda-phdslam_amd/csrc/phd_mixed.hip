@@ -37,14 +37,17 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <cstdint>
+#include <cstring>
 
 #include <hipcub/hipcub.hpp>
 
 #include <vector>
 
 #include "phd_detmath.h"
+#include "phd_kernels.h" /* the block header and the launches the blocks forms share (phd_eap.hip) */
 #include "phd_mixed_k.h"
 
 namespace phd {
@@ -511,7 +514,9 @@ hipError_t mixed_launch_predict_x(const int* slots, int count, const int* src, i
  * serially in priority order by one lane (phd_eap4_*, the oracle's
  * expressions: orc_expected_map_dynamic) — one workgroup over the whole set
  * (dynamic maps are small: no benchmark config uses the mixed model). */
-__global__ void __launch_bounds__(256) k_eap4_gather(const int* __restrict__ src, const float* __restrict__ dmap,
+/* particle blockIdx.x's weighted components into the SoA comp (21 fields of
+ * stride K) at its offset: the single context's gather and the sharded pack */
+__device__ __forceinline__ void eap4_gather_particle(const int* __restrict__ src, const float* __restrict__ dmap,
                                                      const float* __restrict__ dmap_x,
                                                      const int* __restrict__ off, const float* __restrict__ logw,
                                                      int dcap, long K, float* __restrict__ comp) {
@@ -523,6 +528,33 @@ __global__ void __launch_bounds__(256) k_eap4_gather(const int* __restrict__ src
         comp[o + k] = s[k] * ew;  // map[i].weight *= exp(weights[n]) (main.cpp:302-303)
         for (int f = 1; f < PHD_DYN_FIELDS; f++) comp[(size_t)f * K + o + k] = s[(size_t)f * dcap + k];
     }
+}
+
+__global__ void __launch_bounds__(256) k_eap4_gather(const int* __restrict__ src, const float* __restrict__ dmap,
+                                                     const float* __restrict__ dmap_x,
+                                                     const int* __restrict__ off, const float* __restrict__ logw,
+                                                     int dcap, long K, float* __restrict__ comp) {
+    eap4_gather_particle(src, dmap, dmap_x, off, logw, dcap, K, comp);
+}
+
+/* The sharded form's block of this rank ("EAP4", include/phd_capi.h): the
+ * header (workgroup 0) and the gather aimed at the block's fields, stride
+ * K_max — the same product, so the same bits, as the single context's SoA.
+ * off[n] = K_r <= K_max (the host checked it): no entry past the block. */
+__global__ void __launch_bounds__(256) k_eap4_pack(const int* __restrict__ src, const float* __restrict__ dmap,
+                                                   const float* __restrict__ dmap_x,
+                                                   const int* __restrict__ off, const float* __restrict__ logw,
+                                                   int dcap, int n, unsigned int K_max, unsigned int* __restrict__ block) {
+    if (blockIdx.x == 0 && threadIdx.x < EAP_BH_WORDS) {
+        const int t = threadIdx.x;
+        unsigned int v = 0;
+        if (t == EAP_BH_LAYOUT) v = EAP4_BLOCK_LAYOUT;
+        if (t == EAP_BH_COUNT) v = (unsigned int)off[n];
+        if (t == EAP_BH_N) v = (unsigned int)n;
+        if (t == EAP_BH_KMAX) v = K_max;
+        block[t] = v;
+    }
+    eap4_gather_particle(src, dmap, dmap_x, off, logw, dcap, (long)K_max, (float*)(block + EAP_BH_WORDS));
 }
 
 __global__ void k_eap4_iota(unsigned int* a, long n) {
@@ -620,9 +652,8 @@ __global__ void __launch_bounds__(EAP4_NT) k_eap4_merge(const float* __restrict_
     if (tid == 0) *nout = count;
 }
 
-long mixed_expected_map_dynamic(hipStream_t st, const int* d_src, const float* d_dmap, const int* d_dsize,
-                                const float* d_dmap_x, const int* d_dsize_x, int n, int dcap, const float* d_logw, float T, phd_gaussian4d* out, long out_cap,
-                                std::string& err) {
+/* ------------------------------------------------------------------ host */
+
 #define E4CHK(expr)                      \
     do {                                 \
         hipError_t _e = (expr);          \
@@ -631,7 +662,14 @@ long mixed_expected_map_dynamic(hipStream_t st, const int* d_src, const float* d
             return -1;                   \
         }                                \
     } while (0)
-    std::vector<int> src(n), sz((size_t)n), off(n + 1, 0);
+
+/* Per-particle dynamic component counts of a store, clamped to [0, dcap], as
+ * n + 1 host offsets (two read-backs: the slab references, then the sizes they
+ * name).  Returns the component count, -1 on a HIP error (err). */
+static long eap4_offsets(hipStream_t st, const int* d_src, const int* d_dsize, const int* d_dsize_x, int n, int dcap,
+                         std::vector<int>& off, std::string& err) {
+    std::vector<int> src(n);
+    off.assign(n + 1, 0);
     E4CHK(hipMemcpyAsync(src.data(), d_src, n * sizeof(int), hipMemcpyDeviceToHost, st));
     E4CHK(hipStreamSynchronize(st));
     int maxs = 0, maxx = -1;  // the largest slab id named in the current set / in set X
@@ -641,7 +679,7 @@ long mixed_expected_map_dynamic(hipStream_t st, const int* d_src, const float* d
         else
             maxs = std::max(maxs, slab_index(src[p]));
     }
-    if (maxx >= 0 && (!d_dmap_x || !d_dsize_x)) {
+    if (maxx >= 0 && !d_dsize_x) {
         err = "a slab reference names dynamic set X, which is not allocated";
         return -1;
     }
@@ -649,59 +687,213 @@ long mixed_expected_map_dynamic(hipStream_t st, const int* d_src, const float* d
     E4CHK(hipMemcpyAsync(dsz.data(), d_dsize, (maxs + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
     if (maxx >= 0) E4CHK(hipMemcpyAsync(dszx.data(), d_dsize_x, (maxx + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
     E4CHK(hipStreamSynchronize(st));
-    for (int p = 0; p < n; p++)
-        off[p + 1] = off[p] + std::min(std::max(slab_size(src[p], dsz.data(), dszx.data()), 0), dcap);
-    const long K = off[n];
-    if (K == 0) return 0;
+    long K = 0;
+    for (int p = 0; p < n; p++) {
+        K += std::min(std::max(slab_size(src[p], dsz.data(), dszx.data()), 0), dcap);
+        off[p + 1] = (int)std::min<long>(K, 0x7fffffffL);
+    }
+    return K;
+}
+
+/* the reduce's device buffers for K components, carved from one allocation */
+struct Eap4Bufs {
+    float* comp;  // 21 x K SoA weighted components (concatenation order)
+    float* wsorted;
+    unsigned int *i0, *ord, *mem;
+    unsigned char* flag;
+    phd_gaussian4d* out;
+    int* nout;
+    void* tmp;  // hipcub temporary storage
+    size_t tmp_bytes;
+};
+
+static size_t eap4_carve(char* base, long K, size_t tmp, Eap4Bufs* b) {
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        char* q = base ? base + o : nullptr;
+        o = (o + bytes + 255) & ~(size_t)255;
+        return q;
+    };
+    Eap4Bufs t;
+    t.comp = (float*)take((size_t)K * PHD_DYN_FIELDS * 4);
+    t.wsorted = (float*)take((size_t)K * 4);
+    t.i0 = (unsigned int*)take((size_t)K * 4);
+    t.ord = (unsigned int*)take((size_t)K * 4);
+    t.mem = (unsigned int*)take((size_t)K * 4);
+    t.flag = (unsigned char*)take((size_t)K);
+    t.out = (phd_gaussian4d*)take((size_t)K * sizeof(phd_gaussian4d));
+    t.nout = (int*)take(4);
+    t.tmp = take(tmp);
+    t.tmp_bytes = tmp;
+    if (b) *b = t;
+    return o;
+}
+
+static size_t eap4_sort_tmp(long K, hipStream_t st) {
     size_t tmp = 0;
     hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp, (float*)nullptr, (float*)nullptr,
                                                  (unsigned int*)nullptr, (unsigned int*)nullptr, (int)K, 0, 32, st);
-    const size_t bytes = (size_t)(n + 1) * 4 + (size_t)K * (PHD_DYN_FIELDS * 4 + 4 + 4 + 4 + 4 + 1) +
-                         (size_t)K * sizeof(phd_gaussian4d) + tmp + 8 * 256;
+    return tmp;
+}
+
+/* The reduce of a prepared SoA (B.comp: the single context's gather, or the
+ * concatenated blocks of the sharded form): the iota, the stable descending
+ * radix sort, k_eap4_merge, the count read back and the copy out.  Returns the
+ * component count (nothing copied when out is NULL or too small), -1 (err). */
+static long eap4_reduce(hipStream_t st, const Eap4Bufs& B, long K, float T, phd_gaussian4d* out, long out_cap,
+                        std::string& err) {
+    hipLaunchKernelGGL(k_eap4_iota, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, B.i0, K);
+    size_t tb = B.tmp_bytes;
+    E4CHK(hipcub::DeviceRadixSort::SortPairsDescending(B.tmp, tb, B.comp, B.wsorted, B.i0, B.ord, (int)K, 0, 32, st));
+    hipLaunchKernelGGL(k_eap4_merge, dim3(1), dim3(EAP4_NT), 0, st, B.comp, K, B.ord, T, B.flag, B.mem, B.out, B.nout);
+    E4CHK(hipGetLastError());
+    int cnt = 0;
+    E4CHK(hipMemcpyAsync(&cnt, B.nout, 4, hipMemcpyDeviceToHost, st));
+    E4CHK(hipStreamSynchronize(st));
+    if (out && cnt <= out_cap) {
+        E4CHK(hipMemcpyAsync(out, B.out, (size_t)cnt * sizeof(phd_gaussian4d), hipMemcpyDeviceToHost, st));
+        E4CHK(hipStreamSynchronize(st));
+    }
+    return cnt;
+}
+
+long mixed_expected_map_dynamic(hipStream_t st, const int* d_src, const float* d_dmap, const int* d_dsize,
+                                const float* d_dmap_x, const int* d_dsize_x, int n, int dcap, const float* d_logw, float T, phd_gaussian4d* out, long out_cap,
+                                std::string& err) {
+    std::vector<int> off;
+    const long K = eap4_offsets(st, d_src, d_dsize, d_dmap_x ? d_dsize_x : nullptr, n, dcap, off, err);
+    if (K <= 0) return K;
+    if (K >= (1L << 31) - 1) {
+        err = "dynamic expected map: more than 2^31 components";
+        return -1;
+    }
+    const size_t tmp = eap4_sort_tmp(K, st);
+    const size_t head = ((size_t)(n + 1) * 4 + 255) & ~(size_t)255;
     char* buf = nullptr;
-    E4CHK(hipMalloc((void**)&buf, bytes));
-    size_t o = 0;
-    auto take = [&](size_t b) {
-        char* q = buf + o;
-        o = (o + b + 255) & ~(size_t)255;
-        return q;
-    };
-    int* d_off = (int*)take((n + 1) * 4);
-    float* comp = (float*)take((size_t)K * PHD_DYN_FIELDS * 4);
-    float* wsorted = (float*)take((size_t)K * 4);
-    unsigned int* i0 = (unsigned int*)take((size_t)K * 4);
-    unsigned int* ord = (unsigned int*)take((size_t)K * 4);
-    unsigned int* mem = (unsigned int*)take((size_t)K * 4);
-    unsigned char* flag = (unsigned char*)take((size_t)K);
-    phd_gaussian4d* d_out = (phd_gaussian4d*)take((size_t)K * sizeof(phd_gaussian4d));
-    int* d_n = (int*)take(4);
-    void* d_tmp = take(tmp);
+    E4CHK(hipMalloc((void**)&buf, head + eap4_carve(nullptr, K, tmp, nullptr)));
+    int* d_off = (int*)buf;
+    Eap4Bufs B;
+    eap4_carve(buf + head, K, tmp, &B);
     long nout = -1;
-    do {
-        if (hipMemcpyAsync(d_off, off.data(), (n + 1) * 4, hipMemcpyHostToDevice, st) != hipSuccess) break;
+    if (hipMemcpyAsync(d_off, off.data(), (n + 1) * 4, hipMemcpyHostToDevice, st) == hipSuccess) {
         hipLaunchKernelGGL(k_eap4_gather, dim3(n), dim3(256), 0, st, d_src, d_dmap, d_dmap_x, d_off, d_logw, dcap, K,
-                           comp);
-        hipLaunchKernelGGL(k_eap4_iota, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, i0, K);
-        size_t tb = tmp;
-        if (hipcub::DeviceRadixSort::SortPairsDescending(d_tmp, tb, comp, wsorted, i0, ord, (int)K, 0, 32, st) !=
-            hipSuccess)
-            break;
-        hipLaunchKernelGGL(k_eap4_merge, dim3(1), dim3(EAP4_NT), 0, st, comp, K, ord, T, flag, mem, d_out, d_n);
-        if (hipGetLastError() != hipSuccess) break;
-        int cnt = 0;
-        if (hipMemcpyAsync(&cnt, d_n, 4, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipStreamSynchronize(st) != hipSuccess) break;
-        nout = cnt;
-        if (out && cnt <= out_cap)
-            if (hipMemcpyAsync(out, d_out, (size_t)cnt * sizeof(phd_gaussian4d), hipMemcpyDeviceToHost, st) !=
-                    hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess)
-                nout = -1;
-    } while (0);
-    if (nout < 0 && err.empty()) err = hipGetErrorString(hipGetLastError());
+                           B.comp);
+        nout = eap4_reduce(st, B, K, T, out, out_cap, err);
+    } else {
+        err = hipGetErrorString(hipGetLastError());
+    }
+    (void)hipStreamSynchronize(st);  // (an error path may leave work enqueued on buf)
     hipFree(buf);
     return nout;
-#undef E4CHK
 }
+
+/* ------------------------------------------------- the sharded form (blocks)
+ * As for the static map (phd_eap.hip): every rank packs its weighted dynamic
+ * components into a block ("EAP4": header | 21 fields of stride K_max,
+ * include/phd_capi.h), the caller all-gathers the blocks in rank order, every
+ * rank concatenates them into the SoA the single context of all the particles
+ * gathers and runs the same reduce.  The scratch stays with the context. */
+struct Eap4Scratch {
+    char* buf = nullptr;  // the reduce's buffers (eap4_carve), grown on demand
+    size_t bytes = 0;
+    int* d_off = nullptr;    // pack: n + 1 offsets
+    int* pin_off = nullptr;  // their pinned source (the pack does not wait for the upload)
+    int off_n = 0;
+    int* heads = nullptr;  // world + 1 offsets | EAP_HS_WORDS summary words
+    int heads_world = 0;
+    std::vector<int> off;
+    ~Eap4Scratch() {
+        if (buf) (void)hipFree(buf);
+        if (d_off) (void)hipFree(d_off);
+        if (pin_off) (void)hipHostFree(pin_off);
+        if (heads) (void)hipFree(heads);
+    }
+};
+
+void eap4_free(Eap4Scratch* s) { delete s; }
+
+size_t eap4_block_bytes(long K_max) { return eap_block_bytes_of(PHD_DYN_FIELDS, K_max); }
+
+long eap4_shard_count(hipStream_t st, const int* d_src, const int* d_dsize, const int* d_dsize_x, int n, int dcap,
+                      std::string& err) {
+    std::vector<int> off;
+    return eap4_offsets(st, d_src, d_dsize, d_dsize_x, n, dcap, off, err);
+}
+
+int eap4_shard_pack(Eap4Scratch** sp, hipStream_t st, const int* d_src, const float* d_dmap, const int* d_dsize,
+                    const float* d_dmap_x, const int* d_dsize_x, const float* d_logw, int n, int dcap, long K_max,
+                    void* d_block, std::string& err) {
+    if (!*sp) *sp = new Eap4Scratch();
+    Eap4Scratch& S = **sp;
+    const long K_r = eap4_offsets(st, d_src, d_dsize, d_dmap_x ? d_dsize_x : nullptr, n, dcap, S.off, err);
+    if (K_r < 0) return -1;
+    if (K_r > K_max) {
+        err = "the store holds " + std::to_string(K_r) + " dynamic components, K_max is " + std::to_string(K_max);
+        return -2;
+    }
+    // (the stream is idle since eap4_offsets' read-back: the previous pack's upload is consumed)
+    if (S.off_n < n + 1) {
+        if (S.d_off) (void)hipFree(S.d_off);
+        if (S.pin_off) (void)hipHostFree(S.pin_off);
+        S.d_off = S.pin_off = nullptr;
+        S.off_n = 0;
+        E4CHK(hipMalloc((void**)&S.d_off, (size_t)(n + 1) * sizeof(int)));
+        E4CHK(hipHostMalloc((void**)&S.pin_off, (size_t)(n + 1) * sizeof(int), hipHostMallocDefault));
+        S.off_n = n + 1;
+    }
+    memcpy(S.pin_off, S.off.data(), (size_t)(n + 1) * sizeof(int));
+    E4CHK(hipMemcpyAsync(S.d_off, S.pin_off, (size_t)(n + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_eap4_pack, dim3(n), dim3(256), 0, st, d_src, d_dmap, d_dmap_x, (const int*)S.d_off, d_logw,
+                       dcap, n, (unsigned int)K_max, (unsigned int*)d_block);
+    E4CHK(hipGetLastError());
+    return 0;
+}
+
+long mixed_expected_map_dynamic_blocks(Eap4Scratch** sp, hipStream_t st, const void* d_blocks, int world, int n,
+                                       long K_max, float T, phd_gaussian4d* out, long out_cap, std::string& err) {
+    if (!*sp) *sp = new Eap4Scratch();
+    Eap4Scratch& S = **sp;
+    if (S.heads_world < world) {
+        if (S.heads) (void)hipFree(S.heads);
+        S.heads = nullptr;
+        S.heads_world = 0;
+        E4CHK(hipMalloc((void**)&S.heads, (size_t)(world + 1 + EAP_HS_WORDS) * sizeof(int)));
+        S.heads_world = world;
+    }
+    int* d_off = S.heads;
+    unsigned int* d_sum = (unsigned int*)(S.heads + world + 1);
+    const size_t stride_words = eap4_block_bytes(K_max) / 4;
+    eap_launch_block_heads(st, d_blocks, stride_words, world, EAP4_BLOCK_LAYOUT, n, K_max, d_off, d_sum);
+    unsigned int sum[EAP_HS_WORDS];
+    E4CHK(hipMemcpyAsync(sum, d_sum, sizeof(sum), hipMemcpyDeviceToHost, st));
+    E4CHK(hipStreamSynchronize(st));
+    if (sum[EAP_HS_REFUSED] != 0xffffffffu) {
+        err = eap_refused_text(sum[EAP_HS_REFUSED]);
+        return -2;
+    }
+    const unsigned long long total = ((unsigned long long)sum[EAP_HS_TOTAL_HI] << 32) | sum[EAP_HS_TOTAL_LO];
+    if (total == 0) return 0;
+    if (total >= (1ull << 31) - 1) {
+        err = "the blocks hold " + std::to_string(total) + " components, 2^31 - 1 or more";
+        return -2;
+    }
+    const long K = (long)total;
+    const size_t tmp = eap4_sort_tmp(K, st);
+    const size_t need = eap4_carve(nullptr, K, tmp, nullptr);
+    if (S.bytes < need) {
+        if (S.buf) (void)hipFree(S.buf);
+        S.buf = nullptr;
+        S.bytes = 0;
+        E4CHK(hipMalloc((void**)&S.buf, need));
+        S.bytes = need;
+    }
+    Eap4Bufs B;
+    eap4_carve(S.buf, K, tmp, &B);
+    eap_launch_concat(st, d_blocks, stride_words, PHD_DYN_FIELDS, world, K_max, d_off, K, B.comp);
+    E4CHK(hipGetLastError());
+    return eap4_reduce(st, B, K, T, out, out_cap, err);
+}
+
+#undef E4CHK
 
 }  // namespace phd

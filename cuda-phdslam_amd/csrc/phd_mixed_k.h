@@ -86,6 +86,26 @@ long mixed_expected_map_dynamic(hipStream_t st, const int* d_src, const float* d
                                 const float* d_dmap_x, const int* d_dsize_x, int n, int dcap, const float* d_logw, float T, phd_gaussian4d* out, long out_cap,
                                 std::string& err);
 
+/* The sharded form (the "EAP4" block: include/phd_capi.h).  eap4_shard_count:
+ * the dynamic components of the store, clamped per particle to dcap (-1: a HIP
+ * error).  eap4_shard_pack: this rank's block, enqueued after the same
+ * read-back; 0, -1 on a HIP error, -2 when the store holds more than K_max
+ * components (nothing is then written).  mixed_expected_map_dynamic_blocks:
+ * the map of `world` gathered blocks, as mixed_expected_map_dynamic; -2 when a
+ * header is refused (err names the rank; no field is read) or the blocks hold
+ * 2^31 - 1 components or more.  The scratch is the context's, grown on demand
+ * (eap4_free releases it). */
+struct Eap4Scratch;
+void eap4_free(Eap4Scratch* s);
+size_t eap4_block_bytes(long K_max);
+long eap4_shard_count(hipStream_t st, const int* d_src, const int* d_dsize, const int* d_dsize_x, int n, int dcap,
+                      std::string& err);
+int eap4_shard_pack(Eap4Scratch** sp, hipStream_t st, const int* d_src, const float* d_dmap, const int* d_dsize,
+                    const float* d_dmap_x, const int* d_dsize_x, const float* d_logw, int n, int dcap, long K_max,
+                    void* d_block, std::string& err);
+long mixed_expected_map_dynamic_blocks(Eap4Scratch** sp, hipStream_t st, const void* d_blocks, int world, int n,
+                                       long K_max, float T, phd_gaussian4d* out, long out_cap, std::string& err);
+
 }  // namespace phd
 
 #endif /* PHD_MIXED_K_H */

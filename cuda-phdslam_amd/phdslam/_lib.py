@@ -112,6 +112,11 @@ SIGNATURES = {
     "phd_eap_shard_pack": (ctypes.c_int, [_vp, ctypes.c_long, _vp]),
     "phd_expected_map_blocks": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_long, _vp, ctypes.c_long,
                                                ctypes.POINTER(ctypes.c_long)]),
+    "phd_eap_dyn_shard_count": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_long)]),
+    "phd_eap_dyn_shard_block_bytes": (ctypes.c_int, [ctypes.c_long, ctypes.POINTER(ctypes.c_size_t)]),
+    "phd_eap_dyn_shard_pack": (ctypes.c_int, [_vp, ctypes.c_long, _vp]),
+    "phd_expected_map_dynamic_blocks": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_long, _vp, ctypes.c_long,
+                                                       ctypes.POINTER(ctypes.c_long)]),
     # host-only I/O (include/phd_io.h)
     "phd_load_timestamps": (ctypes.c_int, [ctypes.c_char_p, _vp, ctypes.c_int, _c_int_p]),
     "phd_load_controls": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, _vp, ctypes.c_int, _c_int_p]),

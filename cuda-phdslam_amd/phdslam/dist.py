@@ -233,6 +233,7 @@ class ShardedFilter:
         # split PHD part A: phd_wait_logw); the pack waits for the plan
         self.trace_block = self.trace_blocks = None  # enable_trace
         self.eap_block = self.eap_blocks = None  # eap_pack
+        self.eap_dyn_block = self.eap_dyn_blocks = None  # eap_dyn_pack
         self.aux = None
         if overlap and f.update_form():
             self.aux = torch.cuda.Stream(device=device, priority=-1)
@@ -389,6 +390,59 @@ class ShardedFilter:
         """Decision rounds of the last expected_map (the single context's)."""
         return self.f.expected_map_groups()
 
+    # -- the EAP map of the dynamic maps of the whole filter (feature_model 2) --
+    def _eap_dyn_bytes(self, k_max):
+        import ctypes
+        from . import _lib
+        nbytes = ctypes.c_size_t()
+        _lib.check(_lib.lib().phd_eap_dyn_shard_block_bytes(int(k_max), ctypes.byref(nbytes)),
+                   "phd_eap_dyn_shard_block_bytes")
+        return nbytes.value
+
+    def eap_dyn_count(self):
+        """This rank's dynamic component count (the store settled: after flush())."""
+        return self.f.eap_dyn_shard_count()
+
+    def eap_dyn_pack(self, k_max):
+        """This rank's "EAP4" block for the stride k_max (the largest count over
+        the ranks) into eap_dyn_block; eap_dyn_blocks takes the all-gather."""
+        import torch
+        nbytes = self._eap_dyn_bytes(k_max)
+        if self.eap_dyn_block is None or self.eap_dyn_block.numel() != nbytes:
+            self.eap_dyn_block = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self.eap_dyn_blocks = torch.empty(self.world * nbytes, dtype=torch.uint8, device=self.device)
+        self.f.eap_dyn_shard_pack(k_max, self.eap_dyn_block.data_ptr())
+
+    def eap_dyn_finish(self, k_max, out_cap, blocks=None, world=None):
+        """After the all-gather of the blocks (rank order) into eap_dyn_blocks:
+        the dynamic expected map, reduced on this rank.  out_cap: the sum of the
+        counts."""
+        from . import _lib
+        blocks = self.eap_dyn_blocks if blocks is None else blocks
+        world = self.world if world is None else int(world)
+        nbytes = self._eap_dyn_bytes(k_max)
+        if blocks is None or blocks.numel() != world * nbytes:
+            raise _lib.PHDError(_lib.PHD_E_ARG, "ShardedFilter.eap_dyn_finish",
+                                f"{world} blocks of k_max {k_max} are {world * nbytes} bytes, the buffer holds "
+                                f"{0 if blocks is None else blocks.numel()}")
+        return self.f.expected_map_dynamic_blocks(blocks.data_ptr(), world, k_max, out_cap)
+
+    def expected_map_dynamic(self):
+        """The EAP map of the dynamic maps of all world * n particles, on every
+        rank: what PHDFilter.expected_map_dynamic returns on a single mixed
+        context holding the ranks' settled stores in rank order, bit for bit.
+        The phases of expected_map, on buffers of its own: flush, all-gather of
+        the counts, pack, all-gather of the blocks, reduce."""
+        import torch
+        self.flush()
+        mine = torch.tensor([self.eap_dyn_count()], dtype=torch.int64, device=self.device)
+        counts = torch.empty(self.world, dtype=torch.int64, device=self.device)
+        self.comm.all_gather(counts, mine)
+        counts = [int(c) for c in counts.tolist()]
+        self.eap_dyn_pack(max(counts))
+        self.comm.all_gather(self.eap_dyn_blocks, self.eap_dyn_block)
+        return self.eap_dyn_finish(max(counts), sum(counts))
+
     def receive(self):
         """After the all-to-all of the blocks into recv_blocks."""
         self.f.shard_receive_blocks(self.recv_blocks.data_ptr(), self.K, self.recv_rec.data_ptr())
@@ -496,6 +550,20 @@ class GroupRank:
     def expected_map_groups(self):
         return self.f.expected_map_groups()
 
+    def expected_map_dynamic(self):
+        """phd_group_expected_map_dynamic: as ShardedFilter.expected_map_dynamic
+        (a mixed filter; settles the open plan first; the same map on every rank)."""
+        import ctypes
+        import numpy as np
+        from .types import GAUSSIAN4D
+        cap = self.world * self.n * int(self.f.dyn_capacity)
+        out = np.zeros(max(cap, 1), GAUSSIAN4D)
+        nout = ctypes.c_long()
+        _group_check(self.L, self.L.phd_group_expected_map_dynamic(self._g, out.ctypes.data_as(ctypes.c_void_p), cap,
+                                                                   ctypes.byref(nout)),
+                     "phd_group_expected_map_dynamic")
+        return out[:nout.value].copy()
+
     @property
     def stats(self):
         import ctypes
@@ -533,7 +601,8 @@ def group_lib():
                                      ctypes.POINTER(ctypes.c_int)]
         L.phd_group_flush.argtypes = [vp]
         L.phd_group_expected_map.argtypes = [vp, vp, ctypes.c_long, ctypes.POINTER(ctypes.c_long)]
-        L.phd_group_trace_enable.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint]
+        L.phd_group_expected_map_dynamic.argtypes = [vp, vp, ctypes.c_long, ctypes.POINTER(ctypes.c_long)]
+        L.phd_group_trace_enable.argtypes =[vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint]
         L.phd_group_stats.argtypes = [vp, vp]
         L.phd_group_destroy.argtypes = [vp]
         L.phd_group_last_error.restype = ctypes.c_char_p

@@ -33,6 +33,7 @@ class PHDFilter:
         info = Capacity()
         _lib.check(L.phd_ctx_info(h, None, ctypes.byref(info)), "phd_ctx_info")
         self.capacity = info
+        self.dyn_capacity = 0  # enable_dynamic
         self.config = None
         if config is not None:
             self.set_config(config)
@@ -173,6 +174,7 @@ class PHDFilter:
     def enable_dynamic(self, dyn_capacity):
         """Allocate dynamic (Gaussian4D) maps of dyn_capacity components per particle."""
         _lib.check(_lib.lib().phd_enable_dynamic(self._h, int(dyn_capacity)), "phd_enable_dynamic")
+        self.dyn_capacity = int(dyn_capacity)
 
     def load_dynamic(self, maps, offsets):
         """Dynamic maps (flat GAUSSIAN4D + offsets[n+1]); call after load()."""
@@ -532,6 +534,27 @@ class PHDFilter:
         _lib.check(_lib.lib().phd_expected_map_blocks(self._h, ctypes.c_void_p(dev_blocks_ptr), int(world), int(k_max),
                                                       _ptr(out), int(out_cap), ctypes.byref(nout)),
                    "phd_expected_map_blocks")
+        return out[:nout.value]
+
+    def eap_dyn_shard_count(self):
+        """phd_eap_dyn_shard_count: the dynamic components this rank's "EAP4" block will hold."""
+        k = ctypes.c_long()
+        _lib.check(_lib.lib().phd_eap_dyn_shard_count(self._h, ctypes.byref(k)), "phd_eap_dyn_shard_count")
+        return k.value
+
+    def eap_dyn_shard_pack(self, k_max, dev_block_ptr):
+        """phd_eap_dyn_shard_pack: this rank's weighted dynamic components into a device block."""
+        _lib.check(_lib.lib().phd_eap_dyn_shard_pack(self._h, int(k_max), ctypes.c_void_p(dev_block_ptr)),
+                   "phd_eap_dyn_shard_pack")
+
+    def expected_map_dynamic_blocks(self, dev_blocks_ptr, world, k_max, out_cap):
+        """phd_expected_map_dynamic_blocks: the dynamic expected map of `world`
+        gathered blocks (out_cap: the total component count always suffices)."""
+        nout = ctypes.c_long()
+        out = np.zeros(max(int(out_cap), 1), GAUSSIAN4D)
+        _lib.check(_lib.lib().phd_expected_map_dynamic_blocks(self._h, ctypes.c_void_p(dev_blocks_ptr), int(world),
+                                                              int(k_max), _ptr(out), int(out_cap),
+                                                              ctypes.byref(nout)), "phd_expected_map_dynamic_blocks")
         return out[:nout.value]
 
     def update_pending(self, control, step, dev_logw_out_ptr=None, do_predict=True):

@@ -110,7 +110,11 @@ int phd_export_maps(phd_ctx* ctx, int n, const int* offsets, phd_gaussian2d* map
  * follows the slab reference into it; phd_enable_dynamic comes before the
  * record buffers are sized (phd_record_bytes), and with another capacity on a
  * context that holds migrated slabs it leaves them empty dynamic maps, like
- * every other particle's.  Synchronise (except phd_predict_dynamic). */
+ * every other particle's.  On a rank of a sharded filter
+ * phd_expected_map_dynamic and phd_expected_map are that rank's particles'
+ * maps; the filter's two expected maps come from the blocks forms below
+ * (phd_expected_map_dynamic_blocks, phd_expected_map_blocks).  The sharded
+ * trace still refuses the model.  Synchronise (except phd_predict_dynamic). */
 int phd_enable_dynamic(phd_ctx* ctx, int dyn_capacity);
 int phd_load_dynamic_maps(phd_ctx* ctx, int n, const phd_gaussian4d* maps, const int* offsets);
 int phd_dynamic_sizes(phd_ctx* ctx, int* sizes);
@@ -384,13 +388,73 @@ int phd_expected_map_groups(phd_ctx* ctx, int* groups);
  * [1, 1024]; world blocks that do not fit the allocation dev_blocks points
  * into.  Every rank reduces the whole set (as every rank computes the whole
  * plan): about 230 bytes of scratch per component per rank.
- * PHD_E_UNSUPPORTED: feature_model != 0, as the sharded step.
+ * A mixed context (feature_model 2 after phd_enable_dynamic) is served as a
+ * static one: its static maps live in the same slab sets and migration set,
+ * so these calls return the static expected map of the sharded mixed filter
+ * (its dynamic one: the next section).  PHD_E_UNSUPPORTED: feature_model 1,
+ * and feature_model 2 before phd_enable_dynamic.
  * phd_eap_shard_block_bytes is pure arithmetic (no device). */
 int phd_eap_shard_count(phd_ctx* ctx, long* K_local);
 int phd_eap_shard_block_bytes(long K_max, size_t* bytes);
 int phd_eap_shard_pack(phd_ctx* ctx, long K_max, void* dev_block);
 int phd_expected_map_blocks(phd_ctx* ctx, const void* dev_blocks, int world, long K_max, phd_gaussian2d* out,
                             long out_cap, long* n_out);
+
+/* ---- the EAP map of the dynamic maps of a sharded mixed filter ----
+ * phd_expected_map_dynamic's reduce is global in the same way (seeds in weight
+ * order over every particle, ties by concatenation index), so here too the
+ * inputs travel: every rank packs its weighted dynamic components into a
+ * block, the caller all-gathers the blocks in rank order, and every rank
+ * concatenates them and runs phd_expected_map_dynamic's own reduce (a stable
+ * sort and ONE workgroup whose result depends on the concatenated component
+ * array alone).  Every rank then holds, byte for byte and in the same emission
+ * order, what phd_expected_map_dynamic returns on a single mixed context of
+ * world * n particles loaded with the ranks' settled stores in rank order
+ * (rank 0's slots 0 .. n-1, then rank 1's, ...; each particle's components in
+ * slab order, its log-weight as stored).
+ *
+ * The block (phd_eap_dyn_shard_block_bytes: 64 + 84 K_max bytes rounded up to 16):
+ *     bytes 0 .. 63   header, 16 x uint32: [0] layout word 0x34504145 ("EAP4")
+ *                     [1] K_r, this rank's dynamic component count  [4] n
+ *                     [5] K_max (the fields' stride)  every other word zero
+ *     bytes 64 ..     21 float fields of stride K_max, K_r entries each, in the
+ *                     dynamic slab's row order: weight (component weight x
+ *                     exp(log w_p), the single context's phd_det_expf product),
+ *                     mean 0..3, cov 0..15; particles in slot order, components
+ *                     in slab order (a particle's count clamped to
+ *                     [0, dyn_capacity]).  Entries K_r .. K_max-1 are never read.
+ * K_max is the largest K_r over the ranks (any larger value gives the same
+ * result).  Per call the caller makes, with the plan settled (phd_shard_poll ..
+ * phd_update_pending done: the store final):
+ *     phd_eap_dyn_shard_count(ctx, &K_r);  all-gather of the counts;  K_max = max
+ *     phd_eap_dyn_shard_pack(ctx, K_max, dev_block);
+ *     all-gather of dev_block into dev_blocks (rank order), on the context stream;
+ *     phd_expected_map_dynamic_blocks(ctx, dev_blocks, world, K_max, out, out_cap, &n_out);
+ * phd_eap_dyn_shard_count synchronises (it reads back the slab references and
+ * the sizes they name).  phd_eap_dyn_shard_pack makes the same read-back, then
+ * enqueues one kernel on the context stream that reads every particle's
+ * dynamic slab through its slab reference (the dynamic migration set X
+ * included) and writes the fields and the header.  phd_expected_map_dynamic_
+ * blocks checks and scans the headers on the device, concatenates the blocks
+ * into one SoA of Σ K_r components on the context's scratch (kept, grown on
+ * demand) and reduces it; out / out_cap / n_out as phd_expected_map_dynamic
+ * (*n_out written whenever the reduce ran; PHD_E_CAPACITY with nothing copied
+ * when out is NULL or too small; n_out = 0 for an empty set), T = minSeparation
+ * of the context's config.  It synchronises.  Its time is the one-workgroup
+ * reduce's, which grows with the whole filter's dynamic component count.
+ * PHD_E_ARG, before anything is written or any field is read: no
+ * phd_set_config, no phd_enable_dynamic; a null or 16-byte-misaligned buffer;
+ * K_max outside [0, 2^31 - 1); a store with more than K_max dynamic components
+ * (pack); world outside [1, 1024]; world blocks that do not fit the allocation
+ * dev_blocks points into; a header whose layout word, n, stride or count
+ * (K_r > K_max) is wrong — the message names the first such rank and the
+ * reason; 2^31 - 1 components or more in all.
+ * phd_eap_dyn_shard_block_bytes is pure arithmetic (no device). */
+int phd_eap_dyn_shard_count(phd_ctx* ctx, long* K_local);
+int phd_eap_dyn_shard_block_bytes(long K_max, size_t* bytes);
+int phd_eap_dyn_shard_pack(phd_ctx* ctx, long K_max, void* dev_block);
+int phd_expected_map_dynamic_blocks(phd_ctx* ctx, const void* dev_blocks, int world, long K_max, phd_gaussian4d* out,
+                                    long out_cap, long* n_out);
 
 /* ---- per-scan estimate trace on the device ----
  * With the trace on, every phd_step appends one phd_trace_record (phd_types.h)

@@ -88,6 +88,16 @@ int phd_group_flush(phd_group* g);
  * The blocks are allocated here, 28 K_max + 64 bytes per rank, and kept.
  * Synchronises. */
 int phd_group_expected_map(phd_group* g, phd_gaussian2d* out, long out_cap, long* n_out);
+/* The EAP map of the dynamic maps of the whole mixed filter (feature_model 2
+ * after phd_enable_dynamic; phd_capi.h: "the EAP map of the dynamic maps of a
+ * sharded mixed filter"): what phd_expected_map_dynamic returns on a single
+ * mixed context of all world * n particles in rank order, byte for byte.  The
+ * phases of phd_group_expected_map on buffers of its own: the settle,
+ * ncclAllGather of the counts (phd_eap_dyn_shard_count), phd_eap_dyn_shard_pack,
+ * one ncclAllGather of the blocks (84 K_max + 64 bytes per rank, kept), and
+ * phd_expected_map_dynamic_blocks on every rank of this process.  On such a
+ * group phd_group_expected_map returns the static expected map.  Synchronises. */
+int phd_group_expected_map_dynamic(phd_group* g, phd_gaussian4d* out, long out_cap, long* n_out);
 /* Counters over the steps so far: [0] resamples, [1] migrated particles,
  * [2] records sent, [3] records beyond the fixed blocks, [4] pending slots. */
 int phd_group_stats(const phd_group* g, long long* out5);
