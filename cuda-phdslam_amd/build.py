@@ -247,6 +247,35 @@ def build_shim_harness(verbose=False):
                       ["-lphdslam", "-Wl,-rpath,$ORIGIN/../cuda-phdslam_amd/phdslam"], verbose)
 
 
+PROBE_OUT = os.path.join(REPO, "tests", "libcontract_probe.so")
+
+
+def build_contract_probe(verbose=False):
+    """Test-only probe of the shared math / RNG headers (tests/contract_probe.hip
+    -> tests/libcontract_probe.so): each helper alone on the device and on the
+    host.  Compiled with the product's own ARCH, FLAGS and include paths (those
+    of _compile), so the probe sees the headers as the kernels see them; never
+    linked into libphdslam.so."""
+    src = os.path.join(REPO, "tests", "contract_probe.hip")
+    cmd = [hipcc(), f"--offload-arch={ARCH}", *FLAGS, "-I" + os.path.join(REPO, "include"), "-I" + CSRC, "-shared",
+           src]
+    h = hashlib.sha256(" ".join(cmd).encode() + _headers_digest().encode() + _toolchain_id().encode())
+    with open(src, "rb") as fh:
+        h.update(fh.read())
+    key = h.hexdigest()
+    if _up_to_date(PROBE_OUT, key):
+        return PROBE_OUT
+    tmp = PROBE_OUT + f".tmp{os.getpid()}"
+    if verbose:
+        print(" ".join(cmd + ["-o", tmp]), flush=True)
+    subprocess.run(cmd + ["-o", tmp], check=True)
+    os.replace(tmp, PROBE_OUT)
+    with open(PROBE_OUT + f".key.tmp{os.getpid()}", "w") as fh:
+        fh.write(key + "\n")
+    os.replace(PROBE_OUT + f".key.tmp{os.getpid()}", PROBE_OUT + ".key")
+    return PROBE_OUT
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-oracle", action="store_true")
@@ -259,6 +288,7 @@ def main():
     print(build_lib(a.verbose))
     print(build_driver(a.verbose))
     print(build_shim_harness(a.verbose))
+    print(build_contract_probe(a.verbose))
     if a.stamps:
         print(build_stamps_lib(a.verbose))
         print(build_stamps_lib(a.verbose, part_a=True))

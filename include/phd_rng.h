@@ -90,8 +90,20 @@ PHD_HD void phd_box_muller(uint32_t a, uint32_t b, double* n0, double* n1) {
     const double u2 = (double)b * 2.3283064365386963e-10;         /* [0,1) */
     const double rad = PHD_MATH_NS sqrt(-2.0 * PHD_MATH_NS log(u1));
     const double ang = 6.283185307179586476925286766559 * u2;
+#if defined(__GLIBC__) && defined(__cplusplus) && !defined(__HIP_DEVICE_COMPILE__)
+    /* One libm entry whatever the host compiler: g++ -O2 folds cos and sin of
+     * one argument into glibc's sincos(), clang calls the two, and glibc's
+     * sincos is a double ulp from its sin / cos on about 0.1 % of arguments
+     * (tests/test_contract_host.py, box_muller).  The oracle's bits are those
+     * of sincos. */
+    double sn, cs;
+    ::sincos(ang, &sn, &cs);
+    *n0 = rad * cs;
+    *n1 = rad * sn;
+#else
     *n0 = rad * PHD_MATH_NS cos(ang);
     *n1 = rad * PHD_MATH_NS sin(ang);
+#endif
 }
 
 #endif /* PHD_RNG_H */

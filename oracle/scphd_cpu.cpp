@@ -464,6 +464,105 @@ void orc_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
     for (int i = 0; i < 4; i++) out[i] = r.v[i];
 }
 
+/* ---- array forms of the helpers above: the g++ leg of the CPU / gfx950 bit
+ * contract (tests/test_contract_host.py, tests/test_gpu_contract.py).  Record
+ * layouts are those of tests/contract_probe.hip. ---- */
+void orc_arr_det_expf(const float* in, float* out, long n) {
+    for (long i = 0; i < n; i++) out[i] = phd_det_expf(in[i]);
+}
+void orc_arr_det_logf(const float* in, float* out, long n) {
+    for (long i = 0; i < n; i++) out[i] = phd_det_logf(in[i]);
+}
+void orc_arr_det_tanf(const float* in, float* out, long n) {
+    for (long i = 0; i < n; i++) out[i] = phd_det_tanf(in[i]);
+}
+void orc_arr_det_sincosf(const float* in, float* out, long n) {
+    for (long i = 0; i < n; i++) phd_det_sincosf(in[i], &out[2 * i], &out[2 * i + 1]);
+}
+void orc_arr_atan2f(const float* in, float* out, long n) {
+    for (long i = 0; i < n; i++) out[i] = phd_atan2f(in[2 * i], in[2 * i + 1]);
+}
+void orc_arr_wrap(const float* in, float* out, long n) {
+    for (long i = 0; i < n; i++) out[i] = wrapAngle(in[i]);
+}
+void orc_arr_det_safe_log(const float* in, float* out, long n) {
+    for (long i = 0; i < n; i++) out[i] = detSafeLog(in[i]);
+}
+void orc_arr_fix_term(const float* in, uint64_t* out, long n) {
+    for (long i = 0; i < n; i++) out[i] = phd_fix_term(in[i]);
+}
+struct orc_stratum_in {
+    double u;
+    int32_t j, n;
+};
+void orc_arr_fix_stratum(const orc_stratum_in* in, uint64_t* out, long n) {
+    for (long i = 0; i < n; i++) out[i] = phd_fix_stratum(in[i].j, in[i].u, in[i].n);
+}
+void orc_arr_philox4x32_10(const uint32_t* in, uint32_t* out, long n) {
+    for (long i = 0; i < n; i++) {
+        const uint32_t* v = in + 6 * i;
+        phd_u32x4 c = {{v[0], v[1], v[2], v[3]}};
+        phd_u32x4 r = phd_philox4x32_10(c, v[4], v[5]);
+        for (int k = 0; k < 4; k++) out[4 * i + k] = r.v[k];
+    }
+}
+struct orc_draw_in {
+    uint64_t seed, step;
+    uint32_t index, stream;
+};
+void orc_arr_rng_draw(const orc_draw_in* in, uint32_t* out, long n) {
+    for (long i = 0; i < n; i++) {
+        phd_u32x4 r = phd_rng_draw(in[i].seed, in[i].index, in[i].step, in[i].stream);
+        for (int k = 0; k < 4; k++) out[4 * i + k] = r.v[k];
+    }
+}
+void orc_arr_u01(const uint32_t* in, double* out, long n) {
+    for (long i = 0; i < n; i++) out[i] = phd_u01(in[i]);
+}
+void orc_arr_box_muller(const uint32_t* in, double* out, long n) {
+    for (long i = 0; i < n; i++) phd_box_muller(in[2 * i], in[2 * i + 1], &out[2 * i], &out[2 * i + 1]);
+}
+/* in: (px, py, pth, mx, my, P0..P3); out: r, bearing, pd, det, S[4], K[4], cov_update[4] */
+void orc_arr_compute_ekf(const phd_slam_config* cfg, const float* in, float* out, long n) {
+    for (long i = 0; i < n; i++) {
+        const float* v = in + 9 * i;
+        phd_pose pose = {};
+        pose.px = v[0], pose.py = v[1], pose.ptheta = v[2];
+        G2 f = {};
+        f.mean[0] = v[3], f.mean[1] = v[4];
+        for (int k = 0; k < 4; k++) f.cov[k] = v[5 + k];
+        Ekf e;
+        compute_ekf(*cfg, pose, f, e);
+        float* r = out + 16 * i;
+        r[0] = e.r, r[1] = e.bearing, r[2] = e.pd, r[3] = e.det;
+        for (int k = 0; k < 4; k++) r[4 + k] = e.S[k], r[8 + k] = e.K[k], r[12 + k] = e.cov_update[k];
+    }
+}
+/* in: (px, py, pth, range, bearing); out: mean[2], cov[4] */
+void orc_arr_birth(const phd_slam_config* cfg, const float* in, float* out, long n) {
+    for (long i = 0; i < n; i++) {
+        const float* v = in + 5 * i;
+        phd_pose pose = {};
+        pose.px = v[0], pose.py = v[1], pose.ptheta = v[2];
+        phd_measurement z = {};
+        z.range = v[3], z.bearing = v[4];
+        const G2 b = compute_birth(*cfg, pose, z);
+        float* r = out + 6 * i;
+        r[0] = b.mean[0], r[1] = b.mean[1];
+        for (int k = 0; k < 4; k++) r[2 + k] = b.cov[k];
+    }
+}
+/* in: (ax, ay, a0..a3, bx, by, b0..b3) */
+void orc_arr_mahal(const float* in, float* out, long n) {
+    for (long i = 0; i < n; i++) {
+        const float* v = in + 12 * i;
+        G2 a = {}, b = {};
+        a.mean[0] = v[0], a.mean[1] = v[1], b.mean[0] = v[6], b.mean[1] = v[7];
+        for (int k = 0; k < 4; k++) a.cov[k] = v[2 + k], b.cov[k] = v[8 + k];
+        out[i] = mahal(a, b);
+    }
+}
+
 /* Range-bearing h(x) (phdfilter.cu:1841-1845). out = (range, bearing). */
 void orc_measure(const phd_pose* pose, float fx, float fy, float* out) {
     float dx = fx - pose->px, dy = fy - pose->py;
