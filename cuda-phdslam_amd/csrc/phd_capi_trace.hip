@@ -1,7 +1,7 @@
 /*
  * phd_capi_trace.hip — the per-scan estimate trace of the C-ABI (phd_trace.hip
  * holds its kernels): enable, the append of phd_step, reads, and the pack /
- * append pair of the sharded step.
+ * append pairs of the sharded step (static and mixed).
  */
 #include <hip/hip_runtime.h>
 
@@ -265,7 +265,17 @@ int phd_trace_shard_block_bytes(int n, int map_snapshot_cap, int K, size_t* byte
     return PHD_OK;
 }
 
-/* the arguments the three stages of a sharded trace share */
+int phd_trace_shard_block_bytes_mixed(int n, int map_snapshot_cap, int dyn_snapshot_cap, size_t* bytes) {
+    if (n < 1 || map_snapshot_cap < 0 || dyn_snapshot_cap < 0 || !bytes)
+        return fail(PHD_E_ARG, "bad arguments to phd_trace_shard_block_bytes_mixed");
+    *bytes = trace_block_words_mixed(n, map_snapshot_cap, dyn_snapshot_cap) * sizeof(float);
+    return PHD_OK;
+}
+
+}  // extern "C"
+
+/* the arguments the three stages of a sharded trace share; a mixed trace's
+ * carry the dynamic sets (the one current after the update and set X) too */
 static TraceShardArgs trace_shard_args(phd_ctx* ctx, const float* dev_w_all, int world, int rank) {
     auto& T = ctx->tr;
     const size_t slot = (size_t)(T.count % T.cap);
@@ -292,27 +302,50 @@ static TraceShardArgs trace_shard_args(phd_ctx* ctx, const float* dev_w_all, int
     a.rec = T.d_rec + slot;
     a.snap = T.d_snap ? T.d_snap + slot * (size_t)T.snap_cap : nullptr;
     a.card = T.d_card ? T.d_card + slot * (size_t)T.K : nullptr;
+    if (T.mixed) {
+        a.dmap = ctx->mx.d_dmap[ctx->mx.dcur];
+        a.dsize = ctx->mx.d_dsize[ctx->mx.dcur];
+        a.dmap_x = ctx->mx.d_dmap_x;
+        a.dsize_x = ctx->mx.d_dsize_x;
+        a.dcap = ctx->mx.dcap;
+        a.dsnap_cap = T.dsnap_cap;
+        a.block_words = trace_block_words_mixed(ctx->n, a.snap_cap, a.dsnap_cap);
+        a.drec = T.d_drec + slot;
+        a.dsnap = T.d_dsnap ? T.d_dsnap + slot * (size_t)T.dsnap_cap : nullptr;
+    }
     return a;
 }
 
+/* mixed: the call is one of the _mixed pair, which serves a trace enabled by
+ * phd_trace_enable_mixed and no other; the static pair the other way round */
 static int trace_shard_check(phd_ctx* ctx, const void* dev_w_all, const void* dev_block, int world, int rank,
-                             const char* who) {
+                             const char* who, bool mixed) {
     if (!ctx || !dev_w_all || !dev_block || world < 1 || world > 1024 || rank < 0 || rank >= world ||
         (long long)world * ctx->n > (long long)RS_MAX_CHUNKS * RS_THREADS)
         return fail(PHD_E_ARG, std::string("bad arguments to ") + who);
-    if (!ctx->cfg_set || ctx->tr.cap <= 0) return fail(PHD_E_ARG, "the estimate trace is off (phd_trace_enable)");
-    if (ctx->tr.mixed)
+    if (!ctx->cfg_set || ctx->tr.cap <= 0)
+        return fail(PHD_E_ARG, mixed ? "the mixed estimate trace is off (phd_trace_enable_mixed)"
+                                     : "the estimate trace is off (phd_trace_enable)");
+    if (ctx->tr.mixed && !mixed)
         return fail(PHD_E_UNSUPPORTED, std::string(who) + ": a mixed trace (phd_trace_enable_mixed) — the sharded step "
-                                       "does not support feature_model 2");
+                                       "of feature_model 2 is traced by phd_trace_shard_pack_mixed / _append_mixed");
+    if (!ctx->tr.mixed && mixed)
+        return fail(PHD_E_ARG, std::string(who) + ": the trace was enabled by phd_trace_enable (a static trace: "
+                               "phd_trace_shard_pack / _append); the mixed calls need phd_trace_enable_mixed");
     return PHD_OK;
 }
 
-int phd_trace_shard_pack(phd_ctx* ctx, const float* dev_w_all, int world, int rank, uint64_t step, void* dev_block) {
-    int rc = trace_shard_check(ctx, dev_w_all, dev_block, world, rank, "phd_trace_shard_pack");
+static int trace_shard_pack(phd_ctx* ctx, const float* dev_w_all, int world, int rank, uint64_t step, void* dev_block,
+                            const char* who, bool mixed) {
+    int rc = trace_shard_check(ctx, dev_w_all, dev_block, world, rank, who, mixed);
     if (rc) return rc;
     rc = trace_supported(ctx, TRACE_SHARDED);
     if (rc) return rc;
-    if (ctx->tr.shard_packed) return fail(PHD_E_ARG, "phd_trace_shard_append the previous block first");
+    if (ctx->tr.shard_packed)
+        return fail(PHD_E_ARG, mixed ? "phd_trace_shard_append_mixed the previous block first"
+                                     : "phd_trace_shard_append the previous block first");
+    if (mixed && ctx->st.d_map_x && !ctx->mx.d_dmap_x)  // (static records received before phd_enable_dynamic)
+        return fail(PHD_E_ARG, std::string(who) + ": migrated particles without dynamic maps (phd_enable_dynamic comes first)");
     if (set_device(ctx)) return PHD_E_HIP;
     auto& T = ctx->tr;
     if (ctx->sh.stream) {
@@ -338,10 +371,13 @@ int phd_trace_shard_pack(phd_ctx* ctx, const float* dev_w_all, int world, int ra
     return PHD_OK;
 }
 
-int phd_trace_shard_append(phd_ctx* ctx, const float* dev_w_all, const void* dev_blocks_all, int world, int rank) {
-    int rc = trace_shard_check(ctx, dev_w_all, dev_blocks_all, world, rank, "phd_trace_shard_append");
+static int trace_shard_append(phd_ctx* ctx, const float* dev_w_all, const void* dev_blocks_all, int world, int rank,
+                              const char* who, bool mixed) {
+    int rc = trace_shard_check(ctx, dev_w_all, dev_blocks_all, world, rank, who, mixed);
     if (rc) return rc;
-    if (!ctx->tr.shard_packed) return fail(PHD_E_ARG, "phd_trace_shard_append without phd_trace_shard_pack");
+    if (!ctx->tr.shard_packed)
+        return fail(PHD_E_ARG, mixed ? "phd_trace_shard_append_mixed without phd_trace_shard_pack_mixed"
+                                     : "phd_trace_shard_append without phd_trace_shard_pack");
     if (set_device(ctx)) return PHD_E_HIP;
     TraceShardArgs a = trace_shard_args(ctx, dev_w_all, world, rank);
     a.blocks = (const float*)dev_blocks_all;
@@ -350,6 +386,26 @@ int phd_trace_shard_append(phd_ctx* ctx, const float* dev_w_all, const void* dev
     ctx->tr.shard_packed = false;
     ctx->tr.count++;
     return PHD_OK;
+}
+
+extern "C" {
+
+int phd_trace_shard_pack(phd_ctx* ctx, const float* dev_w_all, int world, int rank, uint64_t step, void* dev_block) {
+    return trace_shard_pack(ctx, dev_w_all, world, rank, step, dev_block, "phd_trace_shard_pack", false);
+}
+
+int phd_trace_shard_append(phd_ctx* ctx, const float* dev_w_all, const void* dev_blocks_all, int world, int rank) {
+    return trace_shard_append(ctx, dev_w_all, dev_blocks_all, world, rank, "phd_trace_shard_append", false);
+}
+
+int phd_trace_shard_pack_mixed(phd_ctx* ctx, const float* dev_w_all, int world, int rank, uint64_t step,
+                               void* dev_block) {
+    return trace_shard_pack(ctx, dev_w_all, world, rank, step, dev_block, "phd_trace_shard_pack_mixed", true);
+}
+
+int phd_trace_shard_append_mixed(phd_ctx* ctx, const float* dev_w_all, const void* dev_blocks_all, int world,
+                                 int rank) {
+    return trace_shard_append(ctx, dev_w_all, dev_blocks_all, world, rank, "phd_trace_shard_append_mixed", true);
 }
 
 }  // extern "C"

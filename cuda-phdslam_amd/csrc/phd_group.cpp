@@ -66,6 +66,7 @@ struct phd_group {
     size_t rec = 0;
     int ovf_capacity = 0;
     size_t trace_bytes = 0;  // a rank's trace block (0: the trace is off)
+    bool trace_mixed = false;  // the blocks are the mixed trace's (phd_group_trace_enable_mixed)
     size_t eap_bytes[2] = {0, 0};  // room of a rank's expected-map block, static | dynamic (grown on demand)
     uint64_t seed = 0;
     float new_logw = 0.f;
@@ -370,11 +371,15 @@ int phd_group_step(phd_group* g, const phd_ackerman_control* u, uint64_t step, f
     // (trace on) every rank's trace block, their all-gather, the scan's record:
     // from the store the plan is about to remap and the log-weights it normalises
     if (g->trace_bytes) {
-        for (Rank& k : g->r) PHDCHK(phd_trace_shard_pack(k.ctx, k.w_all, W, k.rank, step, k.tr_block));
+        for (Rank& k : g->r)
+            PHDCHK(g->trace_mixed ? phd_trace_shard_pack_mixed(k.ctx, k.w_all, W, k.rank, step, k.tr_block)
+                                  : phd_trace_shard_pack(k.ctx, k.w_all, W, k.rank, step, k.tr_block));
         NCCLCHK(ncclGroupStart());
         for (Rank& k : g->r) NCCLCHK(ncclAllGather(k.tr_block, k.tr_blocks, g->trace_bytes, ncclUint8, k.comm, k.st));
         NCCLCHK(ncclGroupEnd());
-        for (Rank& k : g->r) PHDCHK(phd_trace_shard_append(k.ctx, k.w_all, k.tr_blocks, W, k.rank));
+        for (Rank& k : g->r)
+            PHDCHK(g->trace_mixed ? phd_trace_shard_append_mixed(k.ctx, k.w_all, k.tr_blocks, W, k.rank)
+                                  : phd_trace_shard_append(k.ctx, k.w_all, k.tr_blocks, W, k.rank));
     }
     // 4. the global plan, identical on every rank; the fixed blocks packed
     for (Rank& k : g->r)
@@ -402,7 +407,10 @@ int phd_group_step(phd_group* g, const phd_ackerman_control* u, uint64_t step, f
     return PHD_OK;
 }
 
-int phd_group_trace_enable(phd_group* g, int capacity, int map_snapshot_cap, unsigned flags) {
+/* phd_group_trace_enable, and with mixed phd_group_trace_enable_mixed: the
+ * contexts' trace and the ranks' blocks, sized by the form's byte count */
+static int group_trace_enable(phd_group* g, int capacity, int map_snapshot_cap, int dyn_snapshot_cap, unsigned flags,
+                              bool mixed) {
     if (!g) return gfail(PHD_E_ARG, "null group");
     for (Rank& k : g->r) {
         (void)hipSetDevice(k.device);
@@ -412,19 +420,37 @@ int phd_group_trace_enable(phd_group* g, int capacity, int map_snapshot_cap, uns
         k.tr_block = k.tr_blocks = nullptr;
     }
     g->trace_bytes = 0;
+    g->trace_mixed = false;
     size_t bytes = 0;
     for (Rank& k : g->r) {
-        PHDCHK(phd_trace_enable(k.ctx, capacity, map_snapshot_cap, flags));
+        if (mixed)
+            PHDCHK(phd_trace_enable_mixed(k.ctx, capacity, map_snapshot_cap, dyn_snapshot_cap, flags));
+        else
+            PHDCHK(phd_trace_enable(k.ctx, capacity, map_snapshot_cap, flags));
         if (!capacity) continue;
-        int card_k = 0;
-        PHDCHK(phd_trace_shape(k.ctx, nullptr, nullptr, &card_k));
-        PHDCHK(phd_trace_shard_block_bytes(g->n, map_snapshot_cap, card_k, &bytes));
+        if (mixed) {
+            PHDCHK(phd_trace_shard_block_bytes_mixed(g->n, map_snapshot_cap, dyn_snapshot_cap, &bytes));
+        } else {
+            int card_k = 0;
+            PHDCHK(phd_trace_shape(k.ctx, nullptr, nullptr, &card_k));
+            PHDCHK(phd_trace_shard_block_bytes(g->n, map_snapshot_cap, card_k, &bytes));
+        }
         HIPCHKG(hipSetDevice(k.device));
         HIPCHKG(hipMalloc((void**)&k.tr_block, bytes));
         HIPCHKG(hipMalloc((void**)&k.tr_blocks, bytes * g->world));
     }
     g->trace_bytes = bytes;
+    g->trace_mixed = mixed && bytes;
     return PHD_OK;
+}
+
+int phd_group_trace_enable(phd_group* g, int capacity, int map_snapshot_cap, unsigned flags) {
+    return group_trace_enable(g, capacity, map_snapshot_cap, 0, flags, false);
+}
+
+int phd_group_trace_enable_mixed(phd_group* g, int capacity, int map_snapshot_cap, int dyn_snapshot_cap,
+                                 unsigned flags) {
+    return group_trace_enable(g, capacity, map_snapshot_cap, dyn_snapshot_cap, flags, true);
 }
 
 int phd_group_flush(phd_group* g) {

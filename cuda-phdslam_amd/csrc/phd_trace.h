@@ -86,15 +86,30 @@ void trace_launch_stage2(const TraceArgs& a, hipStream_t st);
  *   [.., + 7 snap_cap)      the arg-max particle's map snapshot, phd_gaussian2d words
  *   [.., + K)               its cardinality row
  * rounded up to 4 words.  Snapshot and row are zero on the ranks that do not
- * own the arg-max particle.  The all-gathered blocks sit in rank order. */
+ * own the arg-max particle.  The all-gathered blocks sit in rank order.
+ * A mixed-model trace (phd_trace_shard_pack_mixed, K = 0) puts its dynamic half
+ * behind those words, before the rounding:
+ *   [.., + n)               the n local dynamic cardinalities, (float) Σ_j w_j
+ *   [.., + 21 dsnap_cap)    the arg-max particle's dynamic snapshot, phd_gaussian4d words
+ * the whole rounded up to 4 words; the snapshot is zero off the owner. */
 #define TRACE_BH_WORDS 16
 #define TRACE_BH_ERR 0   /* growth of the rank's status-error counter since its previous traced step */
 #define TRACE_BH_OWNER 1 /* 1 on the rank that owns the arg-max particle */
 #define TRACE_BH_SIZE 2  /* owner: components of that particle's map */
 #define TRACE_BH_CARD 3  /* owner: its cardinality (float) */
+#define TRACE_BH_DSIZE 4 /* mixed, owner: components of that particle's dynamic map */
+#define TRACE_BH_DCARD 5 /* mixed, owner: its dynamic cardinality (float) */
 
 inline size_t trace_block_words(int n, int snap_cap, int K) {
     const size_t w = TRACE_BH_WORDS + (size_t)(6 + 1) * n + (size_t)7 * snap_cap + (size_t)K;
+    return (w + 3) & ~(size_t)3;
+}
+/* words of a block in front of its dynamic half (the static block, not rounded) */
+inline size_t trace_block_dyn_offset(int n, int snap_cap, int K) {
+    return TRACE_BH_WORDS + (size_t)(6 + 1) * n + (size_t)7 * snap_cap + (size_t)K;
+}
+inline size_t trace_block_words_mixed(int n, int snap_cap, int dsnap_cap) {
+    const size_t w = trace_block_dyn_offset(n, snap_cap, 0) + (size_t)n + (size_t)21 * dsnap_cap;
     return (w + 3) & ~(size_t)3;
 }
 
@@ -124,15 +139,28 @@ struct TraceShardArgs {
     phd_trace_record* rec;
     phd_gaussian2d* snap;
     float* card;
+    /* the dynamic half of a mixed-model scan (dmap NULL: a static trace): the
+     * dynamic slab set that is current after the update and the dynamic set X
+     * (NULL until the first receive: no reference names it), addressed by the
+     * same slab references as the static sets */
+    const float* dmap;
+    const int* dsize;
+    const float* dmap_x;
+    const int* dsize_x;
+    int dcap, dsnap_cap;
+    phd_trace_dyn_record* drec; /* this scan's entry of the dyn ring */
+    phd_gaussian4d* dsnap;      /* NULL: no dynamic snapshot */
 };
 
 /* Stage 1 (w_all gathered): one 1024-thread workgroup, k_trace_weights'
  * arithmetic over all world * n entries; starts the record. */
 void trace_launch_shard_weights(const TraceShardArgs& a, hipStream_t st);
-/* Stage 2 (posterior maps written, before the plan's remap): this rank's block. */
+/* Stage 2 (posterior maps written, before the plan's remap): this rank's block;
+ * with a.dmap set the mixed form of the kernel, which also writes the dynamic half. */
 void trace_launch_shard_pack(const TraceShardArgs& a, hipStream_t st);
 /* Stage 4 (blocks gathered): the cross-rank sums in the single context's order
- * and the owner's entries; completes the record. */
+ * and the owner's entries; completes the record (a.dmap set: and the dyn
+ * record and snapshot, by one more workgroup). */
 void trace_launch_shard_finish(const TraceShardArgs& a, hipStream_t st);
 
 }  // namespace phd

@@ -24,7 +24,9 @@
  * The sharded step's trace (phd_trace_shard_pack / _append, below): the same
  * record from all world * n particles — k_trace_shard_weights on the gathered
  * log-weights, k_trace_shard_pack into this rank's block, the caller's
- * all-gather of the blocks, k_trace_shard_finish.
+ * all-gather of the blocks, k_trace_shard_finish.  Both come without and with
+ * the dynamic half (phd_trace_shard_pack_mixed / _append_mixed): the static
+ * form carries no dynamic code.
  * No float atomics anywhere: a run reproduces its records bit for bit.
  */
 #include <hip/hip_runtime.h>
@@ -323,10 +325,32 @@ __global__ void __launch_bounds__(RS_THREADS) k_trace_shard_weights(TraceShardAr
     }
 }
 
+/* The dynamic map a slab reference names on a sharded rank: the slab of that
+ * id in the current dynamic set or — bit 30, a migrated particle — in the
+ * dynamic set X (phd_slab.h).  Set X exists from the first receive on, and no
+ * reference names it before. */
+__device__ __forceinline__ Slab dyn_slab_ref(int sref, const TraceShardArgs& a) {
+    return Slab{dyn_slab_map(sref, a.dmap, a.dmap_x, a.dcap), slab_size(sref, a.dsize, a.dsize_x)};
+}
+
+/* Words of one strip of the dynamic snapshot: 64 components as phd_gaussian4d.
+ * The row stride is odd, so a wave's 64 stores of one field — lane k to word
+ * k * 21 + j — fall on distinct LDS banks. */
+#define TRACE_STRIP_WORDS (64 * PHD_DYN_FIELDS)
+
 /* Stage 2: this rank's block.  Workgroup b takes local particles b * TRACE_PB
  * onward, one wave per map at a time; every store runs over consecutive words.
  * Workgroup 0 also writes the header; the snapshot and the cardinality row are
- * dealt over the whole grid. */
+ * dealt over the whole grid.
+ * DYN (a mixed-model trace) adds the dynamic half: the same sum over row 0 of
+ * each particle's dynamic slab, read through its slab reference (dyn_slab_ref),
+ * the owner's dynamic size and cardinality into the header, and the owner's
+ * dynamic snapshot — k_trace_finish's transpose, strips of 64 components dealt
+ * over the grid's waves: each field's 64 values in one coalesced load (zero
+ * past the map's size, and on the ranks that do not own the particle) into the
+ * wave's LDS strip at its phd_gaussian4d word, then the strip's 1344 words to
+ * the block with consecutive lanes on consecutive words. */
+template <bool DYN>
 __global__ void __launch_bounds__(256) k_trace_shard_pack(TraceShardArgs a) {
     __shared__ float s_cn[TRACE_PB];
     __shared__ int s_hdr[TRACE_BH_WORDS];
@@ -363,6 +387,16 @@ __global__ void __launch_bounds__(256) k_trace_shard_pack(TraceShardArgs a) {
             s_hdr[TRACE_BH_ERR] = e >= prev ? e - prev : e;  // (the counter was taken and cleared in between)
             a.hand[TRACE_H_ERRPREV] = e;
         }
+        if constexpr (DYN) {
+            if (wid == 2 && owner) {
+                int sz;
+                const float cn = map_cardinality(dyn_slab_ref(a.hand[TRACE_H_SLAB], a), a.dcap, lane, sz);
+                if (lane == 0) {
+                    s_hdr[TRACE_BH_DSIZE] = sz;
+                    s_hdr[TRACE_BH_DCARD] = __float_as_int(cn);
+                }
+            }
+        }
     }
     __syncthreads();
     if (blockIdx.x == 0 && t < TRACE_BH_WORDS) ((int*)a.block)[t] = s_hdr[t];
@@ -379,7 +413,40 @@ __global__ void __launch_bounds__(256) k_trace_shard_pack(TraceShardArgs a) {
         snap_o[e] = k < rows ? m.map[(size_t)f * a.cap + k] : 0.f;
     }
     for (int k = g; k < a.K; k += stride) row_o[k] = owner && a.card_row ? a.card_row[k] : 0.f;
-    const int used = TRACE_BH_WORDS + 7 * a.n + PHD_NF * a.snap_cap + a.K;  // (the rounding words)
+    int used = TRACE_BH_WORDS + 7 * a.n + PHD_NF * a.snap_cap + a.K;  // (the rounding words)
+    if constexpr (DYN) {
+        __shared__ float s_dcn[TRACE_PB];
+        __shared__ float s_strip[4][TRACE_STRIP_WORDS];
+        float* dcn_o = a.block + used;
+        float* dsnap_o = dcn_o + a.n;
+        used += a.n + PHD_DYN_FIELDS * a.dsnap_cap;
+        for (int q = wid; q < TRACE_PB; q += 4) {
+            const int p = base + q;
+            if (p >= a.n) break;
+            int sz;
+            const float cn = map_cardinality(dyn_slab_ref(a.src[p], a), a.dcap, lane, sz);
+            if (lane == 0) s_dcn[q] = cn;
+        }
+        __syncthreads();
+        if (t < np) dcn_o[base + t] = s_dcn[t];
+        const Slab dm = dyn_slab_ref(a.hand[TRACE_H_SLAB], a);
+        const int drows = owner ? min(min(max(dm.size, 0), a.dcap), a.dsnap_cap) : 0;
+        const int strips = (a.dsnap_cap + 63) >> 6;
+        const size_t dwords = (size_t)a.dsnap_cap * PHD_DYN_FIELDS;
+        for (int s0 = blockIdx.x * 4; s0 < strips; s0 += gridDim.x * 4) {  // (the same trips for the four waves)
+            const int k = (s0 + wid) * 64 + lane;
+            for (int f = 0; f < PHD_DYN_FIELDS; f++) {
+                // Gaussian4D words: cov[0..15] (rows 5..20), mean[0..3] (rows 1..4), weight (row 0)
+                const int j = f >= 5 ? f - 5 : f >= 1 ? 15 + f : 20;
+                s_strip[wid][lane * PHD_DYN_FIELDS + j] = k < drows ? dm.map[(size_t)f * a.dcap + k] : 0.f;
+            }
+            __syncthreads();
+            const size_t w0 = (size_t)(s0 + wid) * TRACE_STRIP_WORDS;
+            for (int e = lane; e < TRACE_STRIP_WORDS; e += 64)
+                if (w0 + e < dwords) dsnap_o[w0 + e] = s_strip[wid][e];
+            __syncthreads();
+        }
+    }
     if (blockIdx.x == 0 && used + t < (int)a.block_words) a.block[used + t] = 0.f;
 }
 
@@ -389,7 +456,42 @@ __global__ void __launch_bounds__(256) k_trace_shard_pack(TraceShardArgs a) {
  * k_trace_card / k_trace_finish's order (partials of TRACE_PB consecutive
  * global indices, term by term; thread t < 256 adds partials t, t + 256, ...;
  * wave scans; the four wave totals in order), then the owner's snapshot and
- * cardinality row into this scan's ring entries. */
+ * cardinality row into this scan's ring entries.
+ * DYN adds workgroup 2: the dynamic card_expected by the same rule over the
+ * gathered dynamic cardinalities, the owner's dynamic card_map and map_size,
+ * the zeroed reserved words, and its dynamic snapshot — already phd_gaussian4d
+ * words in the block — into this scan's entries of the dyn ring. */
+
+/* card_expected over the N = world * n gathered particles, cardinalities at
+ * word cn_at of every rank's block: by threads 0..255 of the workgroup (every
+ * thread calls it; the value is thread 0's). */
+__device__ __forceinline__ float shard_card_expected(const TraceShardArgs& a, size_t cn_at, float lse, double* s_w) {
+    const int t = threadIdx.x;
+    const int n = a.n, N = a.world * n;
+    const int nparts = (N + TRACE_PB - 1) / TRACE_PB;
+    double v = 0.0;
+    if (t < 256)
+        for (int b = t; b < nparts; b += 256) {
+            double s = 0.0;
+            for (int q = 0; q < TRACE_PB; q++) {
+                const int p = b * TRACE_PB + q;
+                double term = 0.0;
+                if (p < N) {
+                    const int r = p / n;
+                    const float cn = a.blocks[(size_t)r * a.block_words + cn_at + (p - r * n)];
+                    term = (double)expf(a.w_all[p] - lse) * (double)cn;
+                }
+                s += term;
+            }
+            v += s;
+        }
+    v = wave_incl_scan_d(v);
+    if (t < 256 && (t & 63) == 63) s_w[t >> 6] = v;
+    __syncthreads();
+    return (float)(((s_w[0] + s_w[1]) + s_w[2]) + s_w[3]);
+}
+
+template <bool DYN>
 __global__ void __launch_bounds__(RS_THREADS) k_trace_shard_finish(TraceShardArgs a) {
     const int t = threadIdx.x;
     const int n = a.n, N = a.world * n;
@@ -400,6 +502,7 @@ __global__ void __launch_bounds__(RS_THREADS) k_trace_shard_finish(TraceShardArg
         const int r = i / n;
         return a.blocks + (size_t)r * a.block_words + TRACE_BH_WORDS + (size_t)6 * (i - r * n);
     };
+    __shared__ double s_w[4];
     if (blockIdx.x == 0) {
         __shared__ double s_r[32];
         float ep[6];
@@ -414,34 +517,28 @@ __global__ void __launch_bounds__(RS_THREADS) k_trace_shard_finish(TraceShardArg
             for (int r = 0; r < a.world; r++) errs += ((const int*)(a.blocks + (size_t)r * a.block_words))[TRACE_BH_ERR];
             a.rec->status_errors = errs;
         }
-    } else {
-        __shared__ double s_w[4];
-        const int nparts = (N + TRACE_PB - 1) / TRACE_PB;
-        double v = 0.0;
-        if (t < 256)
-            for (int b = t; b < nparts; b += 256) {
-                double s = 0.0;
-                for (int q = 0; q < TRACE_PB; q++) {
-                    const int p = b * TRACE_PB + q;
-                    double term = 0.0;
-                    if (p < N) {
-                        const int r = p / n;
-                        const float cn = a.blocks[(size_t)r * a.block_words + TRACE_BH_WORDS + (size_t)6 * n + (p - r * n)];
-                        term = (double)expf(a.w_all[p] - lse) * (double)cn;
-                    }
-                    s += term;
-                }
-                v += s;
-            }
-        v = wave_incl_scan_d(v);
-        if (t < 256 && (t & 63) == 63) s_w[t >> 6] = v;
-        __syncthreads();
-        if (t == 0) a.rec->card_expected = (float)(((s_w[0] + s_w[1]) + s_w[2]) + s_w[3]);
+    } else if (!DYN || blockIdx.x == 1) {
+        const float ce = shard_card_expected(a, TRACE_BH_WORDS + (size_t)6 * n, lse, s_w);
+        if (t == 0) a.rec->card_expected = ce;
         const float* snap_i = own + TRACE_BH_WORDS + (size_t)7 * n;
         if (a.snap)
             for (int e = t; e < a.snap_cap * PHD_NF; e += RS_THREADS) ((float*)a.snap)[e] = snap_i[e];
         if (a.card)
             for (int k = t; k < a.K; k += RS_THREADS) a.card[k] = snap_i[(size_t)PHD_NF * a.snap_cap + k];
+    } else {
+        const size_t dyn_at = TRACE_BH_WORDS + (size_t)7 * n + (size_t)PHD_NF * a.snap_cap + a.K;
+        const float ce = shard_card_expected(a, dyn_at, lse, s_w);
+        if (t == 0) {
+            phd_trace_dyn_record d;
+            d.card_expected = ce;
+            d.card_map = own[TRACE_BH_DCARD];
+            d.map_size = ((const int*)own)[TRACE_BH_DSIZE];
+            for (int i = 0; i < 5; i++) d.reserved[i] = 0;
+            *a.drec = d;
+        }
+        const float* dsnap_i = own + dyn_at + n;
+        if (a.dsnap)
+            for (int e = t; e < a.dsnap_cap * PHD_DYN_FIELDS; e += RS_THREADS) ((float*)a.dsnap)[e] = dsnap_i[e];
     }
 }
 
@@ -450,11 +547,24 @@ void trace_launch_shard_weights(const TraceShardArgs& a, hipStream_t st) {
 }
 
 void trace_launch_shard_pack(const TraceShardArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(k_trace_shard_pack, dim3((a.n + TRACE_PB - 1) / TRACE_PB), dim3(256), 0, st, a);
+    const dim3 grid((a.n + TRACE_PB - 1) / TRACE_PB);
+#if PHD_TRACE_DYN
+    if (a.dmap) {
+        hipLaunchKernelGGL(k_trace_shard_pack<true>, grid, dim3(256), 0, st, a);
+        return;
+    }
+#endif
+    hipLaunchKernelGGL(k_trace_shard_pack<false>, grid, dim3(256), 0, st, a);
 }
 
 void trace_launch_shard_finish(const TraceShardArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(k_trace_shard_finish, dim3(2), dim3(RS_THREADS), 0, st, a);
+#if PHD_TRACE_DYN
+    if (a.dmap) {
+        hipLaunchKernelGGL(k_trace_shard_finish<true>, dim3(3), dim3(RS_THREADS), 0, st, a);
+        return;
+    }
+#endif
+    hipLaunchKernelGGL(k_trace_shard_finish<false>, dim3(2), dim3(RS_THREADS), 0, st, a);
 }
 
 }  // namespace phd

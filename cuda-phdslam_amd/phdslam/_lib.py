@@ -105,6 +105,10 @@ SIGNATURES = {
                                                    ctypes.POINTER(ctypes.c_size_t)]),
     "phd_trace_shard_pack": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _u64, _vp]),
     "phd_trace_shard_append": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int]),
+    "phd_trace_shard_block_bytes_mixed": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                         ctypes.POINTER(ctypes.c_size_t)]),
+    "phd_trace_shard_pack_mixed": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _u64, _vp]),
+    "phd_trace_shard_append_mixed": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int]),
     "phd_expected_map": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.POINTER(ctypes.c_long)]),
     "phd_expected_map_dynamic": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.POINTER(ctypes.c_long)]),
     "phd_eap_shard_count": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_long)]),

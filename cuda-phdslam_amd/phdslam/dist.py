@@ -180,9 +180,10 @@ class ShardedFilter:
          destination) packs FIXED blocks of `block_records` records per peer;
       4. one equal-split all_to_all of the blocks (every step: the host never
          learns the decision before it), and the receive into the deficit slots.
-    With enable_trace, between 3's all_gather and its plan: every rank packs its
-    trace block, one all_gather of the blocks, and the scan's record (the one a
-    single context of all world * n particles writes) joins every rank's ring.
+    With enable_trace (the mixed model: enable_trace_mixed), between 3's
+    all_gather and its plan: every rank packs its trace block, one all_gather of
+    the blocks, and the scan's record (the one a single context of all world * n
+    particles writes) joins every rank's ring.
     flush() settles the last plan (before reading the store on the host).
     Fix the local filter's update form (set_update_form / set_update_threads)
     before constructing: the plan stream beside part C is set up only for the
@@ -231,7 +232,8 @@ class ShardedFilter:
         # the all-gather and the plan on a second, high-priority stream beside the
         # update's part C (its log-weights are final after the CPHD terms / the
         # split PHD part A: phd_wait_logw); the pack waits for the plan
-        self.trace_block = self.trace_blocks = None  # enable_trace
+        self.trace_block = self.trace_blocks = None  # enable_trace / enable_trace_mixed
+        self.trace_mixed = False
         self.eap_block = self.eap_blocks = None  # eap_pack
         self.eap_dyn_block = self.eap_dyn_blocks = None  # eap_dyn_pack
         self.aux = None
@@ -313,6 +315,7 @@ class ShardedFilter:
         import torch
         from . import _lib
         self.trace_block = self.trace_blocks = None
+        self.trace_mixed = False
         if capacity and card_dist and self.f.config.mapEstimate & 2:
             self.f.enable_trace(0)
             raise _lib.PHDError(_lib.PHD_E_UNSUPPORTED, "ShardedFilter.enable_trace",
@@ -327,15 +330,41 @@ class ShardedFilter:
         self.trace_block = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
         self.trace_blocks = torch.empty(self.world * nbytes.value, dtype=torch.uint8, device=self.device)
 
+    def enable_trace_mixed(self, capacity, map_snapshot_cap=0, dyn_snapshot_cap=0):
+        """The estimate trace of the mixed model (PHDFilter.enable_trace_mixed,
+        feature_model 2) on the sharded step: every step() then appends the
+        scan's record and dyn record to the local filter's rings (f.read_trace /
+        f.read_trace_dynamic / f.trace_count) — what a single mixed context of
+        all world * n particles writes.  capacity 0: off, as enable_trace(0).
+        Same arguments on every rank."""
+        import ctypes
+        import torch
+        from . import _lib
+        self.trace_block = self.trace_blocks = None
+        self.trace_mixed = False
+        self.f.enable_trace_mixed(capacity, map_snapshot_cap, dyn_snapshot_cap)
+        if not capacity:
+            return
+        nbytes = ctypes.c_size_t()
+        _lib.check(_lib.lib().phd_trace_shard_block_bytes_mixed(self.n, int(map_snapshot_cap), int(dyn_snapshot_cap),
+                                                                ctypes.byref(nbytes)),
+                   "phd_trace_shard_block_bytes_mixed")
+        self.trace_block = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        self.trace_blocks = torch.empty(self.world * nbytes.value, dtype=torch.uint8, device=self.device)
+        self.trace_mixed = True
+
     def trace_pack(self, k):
         """After gather() and the settle, before plan(): this rank's trace block
-        (the poses, cardinalities and arg-max rows of the store the plan remaps)."""
-        self.f.trace_shard_pack(self.w_all.data_ptr(), self.world, self.rank, k, self.trace_block.data_ptr())
+        (the poses, cardinalities and arg-max rows of the store the plan remaps;
+        with enable_trace_mixed the dynamic cardinalities and rows too)."""
+        pack = self.f.trace_shard_pack_mixed if self.trace_mixed else self.f.trace_shard_pack
+        pack(self.w_all.data_ptr(), self.world, self.rank, k, self.trace_block.data_ptr())
 
     def trace_append(self):
         """After the all-gather of the trace blocks into trace_blocks, before plan()
         (which normalises w_all in place)."""
-        self.f.trace_shard_append(self.w_all.data_ptr(), self.trace_blocks.data_ptr(), self.world, self.rank)
+        append = self.f.trace_shard_append_mixed if self.trace_mixed else self.f.trace_shard_append
+        append(self.w_all.data_ptr(), self.trace_blocks.data_ptr(), self.world, self.rank)
 
     # -- the EAP expected map of the whole filter (phd_capi.h) -------------
     def eap_count(self):
@@ -531,6 +560,13 @@ class GroupRank:
                                                            TRACE_CARD_DIST if card_dist else 0),
                      "phd_group_trace_enable")
 
+    def enable_trace_mixed(self, capacity, map_snapshot_cap=0, dyn_snapshot_cap=0):
+        """phd_group_trace_enable_mixed: as ShardedFilter.enable_trace_mixed
+        (records through the local filter's read_trace / read_trace_dynamic)."""
+        _group_check(self.L, self.L.phd_group_trace_enable_mixed(self._g, int(capacity), int(map_snapshot_cap),
+                                                                 int(dyn_snapshot_cap), 0),
+                     "phd_group_trace_enable_mixed")
+
     def flush(self):
         _group_check(self.L, self.L.phd_group_flush(self._g), "phd_group_flush")
 
@@ -603,6 +639,7 @@ def group_lib():
         L.phd_group_expected_map.argtypes = [vp, vp, ctypes.c_long, ctypes.POINTER(ctypes.c_long)]
         L.phd_group_expected_map_dynamic.argtypes = [vp, vp, ctypes.c_long, ctypes.POINTER(ctypes.c_long)]
         L.phd_group_trace_enable.argtypes =[vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint]
+        L.phd_group_trace_enable_mixed.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint]
         L.phd_group_stats.argtypes = [vp, vp]
         L.phd_group_destroy.argtypes = [vp]
         L.phd_group_last_error.restype = ctypes.c_char_p

@@ -515,6 +515,19 @@ class PHDFilter:
                                                      ctypes.c_void_p(dev_blocks_ptr), int(world), int(rank)),
                    "phd_trace_shard_append")
 
+    def trace_shard_pack_mixed(self, dev_w_all_ptr, world, rank, step, dev_block_ptr):
+        """phd_trace_shard_pack_mixed: this rank's block of the sharded step's
+        mixed trace (enable_trace_mixed): the static block and the dynamic half."""
+        _lib.check(_lib.lib().phd_trace_shard_pack_mixed(self._h, ctypes.c_void_p(dev_w_all_ptr), int(world),
+                                                         int(rank), int(step), ctypes.c_void_p(dev_block_ptr)),
+                   "phd_trace_shard_pack_mixed")
+
+    def trace_shard_append_mixed(self, dev_w_all_ptr, dev_blocks_ptr, world, rank):
+        """phd_trace_shard_append_mixed: the scan's record and dyn record from the gathered blocks."""
+        _lib.check(_lib.lib().phd_trace_shard_append_mixed(self._h, ctypes.c_void_p(dev_w_all_ptr),
+                                                           ctypes.c_void_p(dev_blocks_ptr), int(world), int(rank)),
+                   "phd_trace_shard_append_mixed")
+
     def eap_shard_count(self):
         """phd_eap_shard_count: the components this rank's expected-map block will hold."""
         k = ctypes.c_long()

@@ -113,8 +113,9 @@ int phd_export_maps(phd_ctx* ctx, int n, const int* offsets, phd_gaussian2d* map
  * every other particle's.  On a rank of a sharded filter
  * phd_expected_map_dynamic and phd_expected_map are that rank's particles'
  * maps; the filter's two expected maps come from the blocks forms below
- * (phd_expected_map_dynamic_blocks, phd_expected_map_blocks).  The sharded
- * trace still refuses the model.  Synchronise (except phd_predict_dynamic). */
+ * (phd_expected_map_dynamic_blocks, phd_expected_map_blocks), and its
+ * estimate trace from phd_trace_shard_pack_mixed / _append_mixed.
+ * Synchronise (except phd_predict_dynamic). */
 int phd_enable_dynamic(phd_ctx* ctx, int dyn_capacity);
 int phd_load_dynamic_maps(phd_ctx* ctx, int n, const phd_gaussian4d* maps, const int* offsets);
 int phd_dynamic_sizes(phd_ctx* ctx, int* sizes);
@@ -518,8 +519,9 @@ int phd_trace_shape(phd_ctx* ctx, int* capacity, int* map_snapshot_cap, int* car
  * 2), PHD_TRACE_CARD_DIST (the mixed model has no CPHD), n_predict_particles
  * > 1; from a traced phd_step after feature_model or the dynamic capacity
  * (phd_enable_dynamic) changed — enable the trace again; and from
- * phd_trace_shard_pack / _append (the sharded trace does not support
- * feature_model 2).  Synchronises (an allocation, not a step). */
+ * phd_trace_shard_pack / _append on such a trace (feature_model 2 on the
+ * sharded step is traced by phd_trace_shard_pack_mixed / _append_mixed,
+ * below).  Synchronises (an allocation, not a step). */
 int phd_trace_enable_mixed(phd_ctx* ctx, int capacity, int map_snapshot_cap, int dyn_snapshot_cap, unsigned flags);
 /* The dyn records [first, first + count) into records (count) and dmaps (count
  * x dyn_snapshot_cap, may be NULL), by phd_trace_read's rules: one
@@ -558,12 +560,48 @@ int phd_trace_shape_dynamic(phd_ctx* ctx, int* dyn_snapshot_cap);
  * context stream after the caller's all-gather there, and the plan of a traced
  * step runs after the append, not beside part C.  phd_trace_count / _read
  * serve any rank's context; phd_trace_shard_append advances the count.
- * PHD_E_UNSUPPORTED: what phd_trace_enable refuses, and PHD_TRACE_CARD_DIST
- * with map_estimate & 2 (the expected rows are a sequential float sum over
- * every rank's particles).  world * n <= 2^20 as phd_shard_resample_async. */
+ * PHD_E_UNSUPPORTED: what phd_trace_enable refuses, a mixed trace (its pair
+ * follows), and PHD_TRACE_CARD_DIST with map_estimate & 2 (the expected rows
+ * are a sequential float sum over every rank's particles).  world * n <= 2^20
+ * as phd_shard_resample_async. */
 int phd_trace_shard_block_bytes(int n, int map_snapshot_cap, int K, size_t* bytes);
 int phd_trace_shard_pack(phd_ctx* ctx, const float* dev_w_all, int world, int rank, uint64_t step, void* dev_block);
 int phd_trace_shard_append(phd_ctx* ctx, const float* dev_w_all, const void* dev_blocks_all, int world, int rank);
+
+/* ---- the trace of a sharded step of the mixed model (feature_model 2) ----
+ * With phd_trace_enable_mixed on every rank's context (same arguments), the
+ * sharded step appends BOTH halves to every rank's rings: the scan's
+ * phd_trace_record, its phd_trace_dyn_record and both snapshots, each equal
+ * bit for bit to what the single mixed context of N = world * n particles (the
+ * ranks' settled particles in rank order, same seed) writes in a traced
+ * phd_step.  The calling sequence, the stream hand-off and the pairing of pack
+ * and append are those of phd_trace_shard_pack / _append above; these two
+ * calls replace them, and the all-gathered block is larger.  In 32-bit words:
+ *     the static block above with K = 0, not rounded: 16 + 7 n + 7 map_snapshot_cap
+ *     n dynamic cardinalities, (float) Σ_j w_j of each local particle's dynamic map
+ *     21 dyn_snapshot_cap words: the arg-max particle's dynamic snapshot as
+ *         phd_gaussian4d words, zero past its size and off the owner
+ * rounded up to 4 words — phd_trace_shard_block_bytes_mixed: 64 + 28 n + 28
+ * map_snapshot_cap + 4 n + 84 dyn_snapshot_cap bytes rounded up to 16 (host
+ * arithmetic; PHD_E_ARG on n < 1 or a negative capacity).  Header words 4 and
+ * 5 carry the owner's dynamic map size and dynamic cardinality (zero on the
+ * other ranks).  Every dynamic map is read through its particle's slab
+ * reference: on a rank that holds migrated particles, in the dynamic set X.
+ * On a scan without measurements the record comes from the predicted store
+ * (set X predicted in place), resampled 0.
+ * PHD_E_ARG: no trace, or one enabled by phd_trace_enable (the static pair
+ * serves it); append without pack, pack twice.  PHD_E_UNSUPPORTED: the static
+ * pair on a mixed trace; feature_model or the dynamic capacity changed since
+ * phd_trace_enable_mixed — enable the trace again; n_predict_particles > 1.
+ * A refused call leaves the trace count and the store untouched.  Still
+ * refused on a mixed context: phd_trace_enable, PHD_TRACE_CARD_DIST (no CPHD),
+ * a traced phd_step on migrated slabs; the dynamic EAP map is not part of the
+ * trace. */
+int phd_trace_shard_block_bytes_mixed(int n, int map_snapshot_cap, int dyn_snapshot_cap, size_t* bytes);
+int phd_trace_shard_pack_mixed(phd_ctx* ctx, const float* dev_w_all, int world, int rank, uint64_t step,
+                               void* dev_block);
+int phd_trace_shard_append_mixed(phd_ctx* ctx, const float* dev_w_all, const void* dev_blocks_all, int world,
+                                 int rank);
 
 /* Per-update timing of the fused kernel with HIP events recorded on the
  * context stream around each launch (ring of max_records pairs).

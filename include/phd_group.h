@@ -10,8 +10,9 @@
  *        blocks go point to point (grouped ncclSend / ncclRecv), then
  *        phd_shard_receive_overflow + phd_update_pending on the slots they feed
  *     3. ncclAllGather of the n log-weights (grouped over the ranks)
- *     3t. (phd_group_trace_enable) phd_trace_shard_pack, ncclAllGather of the
- *        trace blocks, phd_trace_shard_append: the scan's estimate record
+ *     3t. (phd_group_trace_enable / _mixed) phd_trace_shard_pack, ncclAllGather
+ *        of the trace blocks, phd_trace_shard_append (the _mixed pair for the
+ *        mixed model): the scan's estimate record
  *     4. phd_shard_resample_async (global normalise / nEff / decision /
  *        parents, identical on every rank; plan; fixed blocks packed)
  *     5. equal-split all-to-all of the blocks (grouped ncclSend / ncclRecv)
@@ -75,6 +76,14 @@ int phd_group_step(phd_group* g, const phd_ackerman_control* u, uint64_t step, f
  * phd_trace_count on any rank's context.  A traced step runs its plan after
  * the trace instead of beside part C.  Synchronises (an allocation). */
 int phd_group_trace_enable(phd_group* g, int capacity, int map_snapshot_cap, unsigned flags);
+/* The same for the mixed model (phd_trace_enable_mixed on every context,
+ * feature_model 2 after phd_enable_dynamic): every phd_group_step then appends
+ * the scan's phd_trace_record and phd_trace_dyn_record, through
+ * phd_trace_shard_pack_mixed / ncclAllGather of the blocks /
+ * phd_trace_shard_append_mixed; read them with phd_trace_read and
+ * phd_trace_read_dynamic.  capacity 0 (here or in phd_group_trace_enable): off. */
+int phd_group_trace_enable_mixed(phd_group* g, int capacity, int map_snapshot_cap, int dyn_snapshot_cap,
+                                 unsigned flags);
 /* Settle the last plan (no update follows): the contexts' stores are final. */
 int phd_group_flush(phd_group* g);
 /* The EAP expected map of the whole filter (phd_capi.h: "the EAP expected map
