@@ -19,8 +19,27 @@ main.cpp:1281-1297 nEff + resample) need every log-weight:
 
 The particle order after a resample is a permutation of the single-GPU order;
 the resampled multiset of particles is the same.
+
+The order of a sharded step's phases is stated once, in ShardedFilter's
+generators (step_phases, settle_phases, expected_map_phases): they run the
+rank-local phases and yield an AllGather, AllToAll or Exchange wherever a
+collective has to happen.  Two drivers serve what they yield: ShardedFilter's
+own step / flush / expected_map through the rank's transport (TorchComm), and
+LocalWorld, which advances the ranks of one process in lockstep and serves the
+collectives with device copies.
 """
+from collections import namedtuple
+
 import numpy as np
+
+# What a phase generator yields: the collective every rank takes part in next.
+# AllGather: `stream` None, or the stream the gather runs on once
+# ready(stream.cuda_stream) has made it wait for `inp`.  AllToAll: equal split,
+# block d of `inp` goes to rank d.  Exchange: point-to-point [(peer, tensor)];
+# yielded with empty lists too, so that the ranks stay aligned.
+AllGather = namedtuple("AllGather", "out inp stream ready")
+AllToAll = namedtuple("AllToAll", "out inp")
+Exchange = namedtuple("Exchange", "sends recvs")
 
 
 def plan_migration(parents, n_local, world):
@@ -185,6 +204,8 @@ class ShardedFilter:
     the blocks, and the scan's record (the one a single context of all world * n
     particles writes) joins every rank's ring.
     flush() settles the last plan (before reading the store on the host).
+    step_phases states this order, the one statement of it in Python; step()
+    serves its collectives through `comm`, LocalWorld through device copies.
     Fix the local filter's update form (set_update_form / set_update_threads)
     before constructing: the plan stream beside part C is set up only for the
     split form found here (a later change stays correct — the all-gather waits
@@ -241,9 +262,9 @@ class ShardedFilter:
             self.aux = torch.cuda.Stream(device=device, priority=-1)
             f.set_plan_stream(self.aux.cuda_stream)
 
-    # The phases are separate methods so the same code runs under
-    # torch.distributed (step) and under a single-process emulation of several
-    # ranks (tests/test_gpu_parity.py::test_sharded_step_matches_single_context).
+    # The rank-local phases are separate methods; the generators below put them
+    # in order, so the same code runs under torch.distributed (step) and as
+    # several ranks of one process (LocalWorld).
     def local_update(self, control, k):
         """predict + update of the local shard (the predict fused into the update
         launch when it pays, as phd_step); log-weights into w_local (device)."""
@@ -280,22 +301,11 @@ class ShardedFilter:
                 self.f.update_pending(control, k, self.w_local.data_ptr())
         self._ovf = ([], [])
 
-    def settle(self, control=None, k=None):
-        out = self.poll()
-        if self._ovf[0] or self._ovf[1]:
-            self.comm.exchange(*self._ovf)
-        self.settle_finish(control, k)
-        return out
-
     def gather(self):
-        """All-gather of the log-weights (beside part C on the plan stream)."""
-        import torch
+        """The all-gather of the log-weights (beside part C on the plan stream)."""
         if self.aux is None:
-            self.comm.all_gather(self.w_all, self.w_local)
-            return
-        self.f.wait_logw(self.aux.cuda_stream)
-        with torch.cuda.stream(self.aux):
-            self.comm.all_gather(self.w_all, self.w_local)
+            return AllGather(self.w_all, self.w_local, None, None)
+        return AllGather(self.w_all, self.w_local, self.aux, self.f.wait_logw)
 
     def plan(self, k):
         """After the all-gather into w_all: the global plan, the fixed send blocks,
@@ -402,18 +412,8 @@ class ShardedFilter:
     def expected_map(self):
         """The EAP expected map of all world * n particles, on every rank: what
         PHDFilter.expected_map returns on a single context holding the ranks'
-        settled stores in rank order, bit for bit.  Settles the open plan
-        (flush), all-gathers the component counts, packs this rank's block,
-        all-gathers the blocks and reduces them locally."""
-        import torch
-        self.flush()
-        mine = torch.tensor([self.eap_count()], dtype=torch.int64, device=self.device)
-        counts = torch.empty(self.world, dtype=torch.int64, device=self.device)
-        self.comm.all_gather(counts, mine)
-        counts = [int(c) for c in counts.tolist()]
-        self.eap_pack(max(counts))
-        self.comm.all_gather(self.eap_blocks, self.eap_block)
-        return self.eap_finish(max(counts), sum(counts))
+        settled stores in rank order, bit for bit (expected_map_phases)."""
+        return self._serve(self.expected_map_phases(False))
 
     def expected_map_groups(self):
         """Decision rounds of the last expected_map (the single context's)."""
@@ -459,22 +459,75 @@ class ShardedFilter:
     def expected_map_dynamic(self):
         """The EAP map of the dynamic maps of all world * n particles, on every
         rank: what PHDFilter.expected_map_dynamic returns on a single mixed
-        context holding the ranks' settled stores in rank order, bit for bit.
-        The phases of expected_map, on buffers of its own: flush, all-gather of
-        the counts, pack, all-gather of the blocks, reduce."""
-        import torch
-        self.flush()
-        mine = torch.tensor([self.eap_dyn_count()], dtype=torch.int64, device=self.device)
-        counts = torch.empty(self.world, dtype=torch.int64, device=self.device)
-        self.comm.all_gather(counts, mine)
-        counts = [int(c) for c in counts.tolist()]
-        self.eap_dyn_pack(max(counts))
-        self.comm.all_gather(self.eap_dyn_blocks, self.eap_dyn_block)
-        return self.eap_dyn_finish(max(counts), sum(counts))
+        context holding the ranks' settled stores in rank order, bit for bit
+        (expected_map_phases, on buffers of its own)."""
+        return self._serve(self.expected_map_phases(True))
 
     def receive(self):
         """After the all-to-all of the blocks into recv_blocks."""
         self.f.shard_receive_blocks(self.recv_blocks.data_ptr(), self.K, self.recv_rec.data_ptr())
+
+    # -- the order of the phases, and the collectives between them ----------
+    def settle_phases(self, control=None, k=None):
+        """Settle the open plan: poll, the overflow transfers, settle_finish."""
+        out = self.poll()
+        yield Exchange(*self._ovf)
+        self.settle_finish(control, k)
+        return out
+
+    def step_phases(self, control, k):
+        """One sharded step; returns what step() returns."""
+        self.local_update(control, k)
+        prev = yield from self.settle_phases(control, k)
+        yield self.gather()
+        if self.trace_block is not None:
+            self.trace_pack(k)
+            yield AllGather(self.trace_blocks, self.trace_block, None, None)
+            self.trace_append()
+        self.plan(k)
+        yield AllToAll(self.recv_blocks, self.send_blocks)
+        self.receive()
+        return prev
+
+    def expected_map_phases(self, dynamic):
+        """The static (dynamic: the dynamic) expected map: settle the open plan,
+        all-gather the component counts, pack this rank's block at the largest,
+        all-gather the blocks, reduce them locally."""
+        import torch
+        count, pack, finish = ((self.eap_dyn_count, self.eap_dyn_pack, self.eap_dyn_finish) if dynamic else
+                               (self.eap_count, self.eap_pack, self.eap_finish))
+        yield from self.settle_phases(None, None)
+        mine = torch.tensor([count()], dtype=torch.int64, device=self.device)
+        counts = torch.empty(self.world, dtype=torch.int64, device=self.device)
+        yield AllGather(counts, mine, None, None)
+        counts = [int(c) for c in counts.tolist()]
+        pack(max(counts))
+        if dynamic:
+            yield AllGather(self.eap_dyn_blocks, self.eap_dyn_block, None, None)
+        else:
+            yield AllGather(self.eap_blocks, self.eap_block, None, None)
+        return finish(max(counts), sum(counts))
+
+    def _serve(self, phases):
+        """Run a phase generator on this rank, its collectives through comm."""
+        comm = self.comm
+        try:
+            while True:
+                c = next(phases)
+                if type(c) is Exchange:
+                    if c.sends or c.recvs:
+                        comm.exchange(c.sends, c.recvs)
+                elif type(c) is AllToAll:
+                    comm.all_to_all_equal(c.out, c.inp)
+                elif c.stream is None:
+                    comm.all_gather(c.out, c.inp)
+                else:
+                    import torch
+                    c.ready(c.stream.cuda_stream)
+                    with torch.cuda.stream(c.stream):
+                        comm.all_gather(c.out, c.inp)
+        except StopIteration as done:
+            return done.value
 
     def step(self, control, k):
         """One sharded filter step.  Returns (neff, resampled) of the PREVIOUS
@@ -482,21 +535,103 @@ class ShardedFilter:
         (the current step's plan is polled by the next step, or by flush()); the
         first step returns (None, None).  The device store is final only after
         flush()."""
-        self.local_update(control, k)
-        prev = self.settle(control, k)
-        self.gather()
-        if self.trace_block is not None:
-            self.trace_pack(k)
-            self.comm.all_gather(self.trace_blocks, self.trace_block)
-            self.trace_append()
-        self.plan(k)
-        self.comm.all_to_all_equal(self.recv_blocks, self.send_blocks)
-        self.receive()
-        return prev
+        return self._serve(self.step_phases(control, k))
+
+    def settle(self, control=None, k=None):
+        return self._serve(self.settle_phases(control, k))
 
     def flush(self):
         """Settle the last plan (no update follows): the store is then final."""
-        return self.settle(None, None)
+        return self._serve(self.settle_phases(None, None))
+
+
+class LocalWorld:
+    """The `world` ranks of a sharded filter in one process on one device:
+    ShardedFilter(f, None, device, world=..., rank=r) for r = 0 .. world - 1,
+    without a transport of their own.  Every call advances each rank's phase
+    generator to its next collective, requires all ranks to have arrived at the
+    same kind, and serves it with device copies between the ranks' buffers.
+    Each returns the ranks' results in rank order."""
+
+    def __init__(self, shards):
+        self.shards = list(shards)
+        for r, sf in enumerate(self.shards):
+            if sf.rank != r or sf.world != len(self.shards):
+                raise ValueError(f"shard {r} of {len(self.shards)} is rank {sf.rank} of world {sf.world}")
+
+    def step(self, control, k):
+        return self._serve([sf.step_phases(control, k) for sf in self.shards])
+
+    def flush(self):
+        return self._serve([sf.settle_phases(None, None) for sf in self.shards])
+
+    def expected_map(self):
+        return self._serve([sf.expected_map_phases(False) for sf in self.shards])
+
+    def expected_map_dynamic(self):
+        return self._serve([sf.expected_map_phases(True) for sf in self.shards])
+
+    def _serve(self, phases):
+        results = [None] * len(phases)
+        while True:
+            calls = []
+            for r, g in enumerate(phases):
+                try:
+                    calls.append(next(g))
+                except StopIteration as done:
+                    results[r] = done.value
+                    calls.append(None)
+            kinds = set(type(c) for c in calls)
+            if len(kinds) != 1:
+                raise RuntimeError("the ranks diverged: " + ", ".join(
+                    f"rank {r} {'returned' if c is None else 'at ' + type(c).__name__}" for r, c in enumerate(calls)))
+            if calls[0] is None:
+                return results
+            _LOCAL[kinds.pop()](calls)
+
+
+def local_all_gather(calls):
+    """The ranks' inputs, in rank order, into every rank's output.  On a rank's
+    stream: after every rank's input is ready for that stream."""
+    import torch
+    for c in calls:
+        if c.stream is None:
+            c.out.copy_(torch.cat([o.inp for o in calls]))
+            continue
+        for o in calls:
+            o.ready(c.stream.cuda_stream)
+        with torch.cuda.stream(c.stream):
+            c.out.copy_(torch.cat([o.inp for o in calls]))
+
+
+def local_all_to_all(calls):
+    """Block d of every rank to rank d, in source-rank order."""
+    import torch
+    blk = calls[0].inp.numel() // len(calls)
+    if blk == 0:
+        return
+    for d, c in enumerate(calls):
+        c.out.copy_(torch.cat([s.inp[d * blk:(d + 1) * blk] for s in calls]))
+
+
+def local_exchange(calls):
+    """Every receive buffer of rank r from source s takes the one send of s
+    addressed to r; every send is taken."""
+    taken = 0
+    for r, c in enumerate(calls):
+        for s, buf in c.recvs:
+            src = [t for d, t in calls[s].sends if d == r]
+            if len(src) != 1:
+                raise RuntimeError(f"rank {r} receives from rank {s}, which has {len(src)} sends for it")
+            if src[0].numel() != buf.numel():
+                raise RuntimeError(f"rank {s} sends {src[0].numel()} elements to rank {r}, which expects {buf.numel()}")
+            buf.copy_(src[0])
+            taken += 1
+    if taken != sum(len(c.sends) for c in calls):
+        raise RuntimeError(f"{sum(len(c.sends) for c in calls)} sends for {taken} receives")
+
+
+_LOCAL = {AllGather: local_all_gather, AllToAll: local_all_to_all, Exchange: local_exchange}
 
 
 class GroupRank:

@@ -1,8 +1,8 @@
 """Cost of the estimate trace on the sharded step of the mixed model (DESIGN.md
 §6 "Mixed model", *Trace*): the (world, n, K) = (2, 24, 4) shape of that
 section's timing — mixed_scenario with 30 static and 10 dynamic components, 10
-measurements, a resample every step, both ranks emulated on one device, the
-collectives as device copies — untraced and traced with snapshots (8, 16);
+measurements, a resample every step, both ranks on one device under
+phdslam.dist.LocalWorld (the collectives as device copies) — untraced and traced with snapshots (8, 16);
 host wall clock around a synchronised step, 40 steps after 5, min / median /
 max in ms and the bytes of one trace block, one JSON line.
 
@@ -21,43 +21,10 @@ sys.path[:0] = [os.path.join(REPO, "cuda-phdslam_amd")]
 
 import torch  # noqa: E402
 import phdslam  # noqa: E402
-from phdslam.dist import ShardedFilter  # noqa: E402
+from phdslam.dist import LocalWorld, ShardedFilter  # noqa: E402
 from phdslam.scenario import mixed_config, mixed_scenario  # noqa: E402
 
 SEED = 0x5eed
-
-
-def settle(shards, ctrl, k):
-    for sf in shards:
-        sf.poll()
-    for r, sf in enumerate(shards):  # point-to-point overflow transfers
-        for s_, buf in sf._ovf[1]:
-            buf.copy_([t for d, t in shards[s_]._ovf[0] if d == r][0])
-    for sf in shards:
-        sf.settle_finish(ctrl, k)
-
-
-def step(shards, k):
-    """ShardedFilter.step of every emulated rank."""
-    for sf in shards:
-        sf.local_update(None, k)
-    settle(shards, None, k)
-    w = torch.cat([o.w_local for o in shards])
-    for sf in shards:
-        sf.w_all.copy_(w)
-    if shards[0].trace_block is not None:
-        for sf in shards:
-            sf.trace_pack(k)
-        blocks = torch.cat([sf.trace_block for sf in shards])
-        for sf in shards:
-            sf.trace_blocks.copy_(blocks)
-            sf.trace_append()
-    for sf in shards:
-        sf.plan(k)
-    blk = shards[0].K * shards[0].record_bytes
-    for d, sf in enumerate(shards):
-        sf.recv_blocks.copy_(torch.cat([src.send_blocks[d * blk:(d + 1) * blk] for src in shards]))
-        sf.receive()
 
 
 def run(world, n, K, trace, steps=40, warm=5):
@@ -82,15 +49,16 @@ def run(world, n, K, trace, steps=40, warm=5):
         if trace:
             sf.enable_trace_mixed(64, *trace)
         shards.append(sf)
+    ranks = LocalWorld(shards)
     ts = []
     for k in range(1, warm + steps + 1):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        step(shards, k)
+        ranks.step(None, k)
         torch.cuda.synchronize()
         if k > warm:
             ts.append((time.perf_counter() - t0) * 1e3)
-    settle(shards, None, None)
+    ranks.flush()
     torch.cuda.synchronize()
     res = {"min_ms": round(min(ts), 4), "median_ms": round(statistics.median(ts), 4), "max_ms": round(max(ts), 4),
            "steps": steps, "resamples": shards[0].stats["resamples"]}

@@ -12,11 +12,11 @@ one workgroup (k_eap4_merge), so its result depends on the concatenated
 component array alone: every comparison below is byte equality of the
 returned arrays; no tolerance is involved.
 
-Emulated ranks on one device, with the helpers of tests/test_eap_sharded.py
-(the thread-per-rank transport) and tests/test_gpu_mixed_sharded.py (the
-mixed filters, stores and the stepped chain).  The hand-built cases drive the
-phases (eap_dyn_count, eap_dyn_pack, eap_dyn_finish) with the all-gather as
-torch.cat; the chains call ShardedFilter.expected_map_dynamic itself.
+Emulated ranks on one device (phdslam.dist.LocalWorld), with the helpers of
+tests/test_gpu_mixed_sharded.py (the mixed filters, stores and the stepped
+chain).  The hand-built cases drive the phases (eap_dyn_count, eap_dyn_pack,
+eap_dyn_finish) with the all-gather as torch.cat; the chains run
+ShardedFilter's own expected-map phases (LocalWorld.expected_map_dynamic).
 """
 import ctypes
 
@@ -27,6 +27,7 @@ import test_eap_sharded as tes
 import test_gpu_mixed_sharded as tms
 
 from phdslam.scenario import mixed_config, mixed_scenario
+from sharded_helpers import gathered_mixed, slice_mixed
 
 DCAP = 16  # dynamic capacity of the hand-built stores
 N = 8      # their particles per rank
@@ -229,7 +230,7 @@ def test_global_greedy_is_needed(gpu):
     cfg = mixed_config()
     poses, sm, sof, dm, dof, _ = mixed_scenario(cfg, 2 * N, 3, 6, 4, seed=4711)
     lw = np.random.default_rng(5).normal(-np.log(2 * N), 0.4, 2 * N).astype(np.float32)
-    stores = [tms._slice(poses, lw, sm, sof, dm, dof, r * N, (r + 1) * N) for r in range(2)]
+    stores = [slice_mixed(poses, lw, sm, sof, dm, dof, r * N, (r + 1) * N) for r in range(2)]
     shards = _shards(cfg, stores, dcap=DCAP)
     per_rank = np.concatenate([sf.f.expected_map_dynamic() for sf in shards])
     eaps, counts, _, _ = _phases(shards)
@@ -321,28 +322,29 @@ def test_all_ranks_empty(gpu):
 def test_after_migration(gpu, monkeypatch, world, n, K):
     """Three sharded steps of the mixed model (a resample every step; K = 0:
     every record late, its slabs in the sets X), then both expected maps of
-    the filter from ShardedFilter on every rank, one thread per rank, against
-    a fresh single mixed context loaded with the gathered stores."""
+    the filter from ShardedFilter on every rank (LocalWorld), against a fresh
+    single mixed context loaded with the gathered stores."""
+    from phdslam.dist import LocalWorld
     sent_before = []
-    step = tms._emulated_step
+    steps = []
+    step = LocalWorld.step
 
-    def counting_step(shards, ctrl, k, dev):
-        sent_before[:] = [sf.stats["records"] for sf in shards]  # the steps before this one (each is polled in turn)
-        step(shards, ctrl, k, dev)
+    def counting_step(ranks, ctrl, k):
+        sent_before[:] = [sf.stats["records"] for sf in ranks.shards]  # the steps before this one (each is polled in turn)
+        steps.append(k)
+        return step(ranks, ctrl, k)
 
-    monkeypatch.setattr(tms, "_emulated_step", counting_step)
+    monkeypatch.setattr(LocalWorld, "step", counting_step)
     seen = {}
 
     def after(cfg, shards):
-        gathered = tms._gathered([sf.f for sf in shards])
+        gathered = gathered_mixed([sf.f for sf in shards])
         single = tms._filter(cfg, world * n)
         tms._load(single, *gathered)
         want_dyn, want_static = single.expected_map_dynamic().copy(), single.expected_map().copy()
         single.close()
-        hub = tes._Hub(world)
-        for r, sf in enumerate(shards):
-            sf.comm = tes._RankComm(hub, r)
-        got = tes._on_every_rank(shards, hub, lambda sf: (sf.expected_map_dynamic(), sf.expected_map()))
+        ranks = LocalWorld(shards)
+        got = list(zip(ranks.expected_map_dynamic(), ranks.expected_map()))
         assert 0 < len(want_dyn) < int(gathered[5][-1]) and 0 < len(want_static) < int(gathered[3][-1])
         for r in range(world):
             _same(got[r][0], want_dyn, f"rank {r}: dynamic map vs single context")
@@ -352,6 +354,7 @@ def test_after_migration(gpu, monkeypatch, world, n, K):
         seen["last_sent"] = [sf.stats["records"] - b for sf, b in zip(shards, sent_before)]
 
     pending, moved = tms._sharded_vs_single(world, n, K, after=after)
+    assert steps == [1, 2, 3]
     assert moved > 0
     if K == 0:
         assert pending > 0

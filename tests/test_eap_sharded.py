@@ -16,21 +16,20 @@ reported 7, 6 and 6 rounds and the single context 5, with identical maps.
 What is fixed is asserted: 1 for the exhaustive greedy (non-finite input),
 more than 3 on the chains layout, at least 1 otherwise.
 
-Emulated ranks on one device (the pattern and the helpers of
-tests/test_trace_sharded.py).  The chain test calls ShardedFilter.expected_map
-itself on every rank, one thread per rank, with a transport whose collectives
-are device copies between the threads; the hand-built cases drive the phases
-(eap_count, eap_pack, eap_finish) with the all-gathers as torch.cat.
+Emulated ranks on one device (phdslam.dist.LocalWorld, the scenarios of
+tests/test_trace_sharded.py).  The chain test runs ShardedFilter's own
+expected-map phases on every rank in lockstep (LocalWorld.expected_map); the
+hand-built cases drive the phases (eap_count, eap_pack, eap_finish) with the
+all-gathers as torch.cat.
 """
 import ctypes
 import functools
-import queue
-import threading
 
 import numpy as np
 import pytest
 
 import test_trace_sharded as tts
+from sharded_helpers import gathered_store, slice_store
 
 CAP = tts.CAP
 T_SEP = 10.0  # minSeparation of the hand-built cases (tests/test_gpu_parity.py::test_expected_map_edge_cases)
@@ -93,58 +92,6 @@ def _single(c, state, **cap):
     return eap, rounds
 
 
-class _Hub:
-    """The transport of `world` emulated ranks, one thread each: an all-gather
-    is a barrier and a device copy of the ranks' buffers (every rank enqueues
-    on the same stream, so a copy follows the kernels that wrote its source);
-    a point-to-point transfer hands the sender's buffer to the receiver."""
-
-    def __init__(self, world):
-        self.world = world
-        self.barrier = threading.Barrier(world, timeout=120)
-        self.slots = [None] * world
-        self.p2p = {(s, d): queue.Queue() for s in range(world) for d in range(world)}
-
-
-class _RankComm:
-    def __init__(self, hub, rank):
-        self.hub, self.rank = hub, rank
-
-    def all_gather(self, out, inp):
-        import torch
-        self.hub.slots[self.rank] = inp
-        self.hub.barrier.wait()
-        out.copy_(torch.cat([s.reshape(-1) for s in self.hub.slots]))
-        self.hub.barrier.wait()
-
-    def exchange(self, sends, recvs):
-        for d, t in sends:
-            self.hub.p2p[(self.rank, d)].put(t)
-        for s, buf in recvs:
-            buf.copy_(self.hub.p2p[(s, self.rank)].get(timeout=120))
-
-
-def _on_every_rank(shards, hub, fn):
-    """fn(sf) on one thread per rank; the results in rank order."""
-    out, errs = [None] * len(shards), []
-
-    def run(r):
-        try:
-            out[r] = fn(shards[r])
-        except BaseException as e:  # noqa: BLE001 (re-raised below)
-            errs.append(e)
-            hub.barrier.abort()
-
-    threads = [threading.Thread(target=run, args=(r,)) for r in range(len(shards))]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
-    if errs:
-        raise errs[0]
-    return out
-
-
 @functools.lru_cache(maxsize=None)
 def _chain(cid, world, K):
     """Five free-running sharded scans (the scenario, thresholds and seeds of
@@ -152,34 +99,33 @@ def _chain(cid, world, K):
     last plan still open.  Computed once per case, never modified."""
     import torch
     import pyoracle
-    from phdslam.dist import ShardedFilter
+    from phdslam.dist import LocalWorld, ShardedFilter
     n = 48
     N = world * n
     # the seeds of test_trace_sharded.py: with every one of these the chain
     # resamples and at least one particle migrates (asserted by the test)
     c, state, z = tts._scenario(cid, N, tts.SEED.get((cid, world, n)))
     dev = torch.device("cuda", 0)
-    hub = _Hub(world)
     shards = []
     for r in range(world):
         f = tts._filter(c, n)
         f.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        f.load(*tts._slice(state, r * n, (r + 1) * n))
-        shards.append(ShardedFilter(f, None, dev, world=world, rank=r, seed=tts.FILTER_SEED, block_records=K,
-                                    comm=_RankComm(hub, r)))
+        f.load(*slice_store(state, r * n, (r + 1) * n))
+        shards.append(ShardedFilter(f, None, dev, world=world, rank=r, seed=tts.FILTER_SEED, block_records=K))
+    ranks = LocalWorld(shards)
     ctrl = tts._control(c)
     for k in range(1, tts.SCANS + 1):
         for sf in shards:
             sf.f.set_measurements(z)
-        tts._emulated_step(shards, ctrl, k)
+        ranks.step(ctrl, k)
     assert all(sf._open for sf in shards), "the last plan is open: expected_map() settles it"
-    eaps = _on_every_rank(shards, hub, lambda sf: sf.expected_map())
+    eaps = ranks.expected_map()
     rounds = [sf.expected_map_groups() for sf in shards]
     torch.cuda.synchronize()
     assert not any(sf._open for sf in shards)
     stats = {k: sum(sf.stats[k] for sf in shards) for k in shards[0].stats}
     stats["resamples"] = shards[0].stats["resamples"]
-    gathered = tts._gathered(shards)
+    gathered = gathered_store([sf.f for sf in shards])
     for sf in shards:
         sf.f.close()
     single, rounds1 = _single(c, gathered)

@@ -10,8 +10,8 @@ plan's sums are canonical, so every comparison below is byte equality; no
 tolerance is involved.
 
 Every rank is emulated on one device: ShardedFilter(f, None, dev, world=…,
-rank=…) with the collectives as device copies between the ranks' buffers (the
-helpers of tests/test_gpu_parity.py, restated here).  Capacities as
+rank=…) under phdslam.dist.LocalWorld, which serves the collectives as device
+copies between the ranks' buffers.  Capacities as
 tests/test_gpu_mixed.py: cap 128, dcap 64, M 32, K 4096; resampleThresh 1.0
 (a resample every step with measurements).
 
@@ -28,6 +28,7 @@ import numpy as np
 import pytest
 
 from phdslam.scenario import mixed_config, mixed_scenario
+from sharded_helpers import gathered_mixed, slice_mixed
 
 CAP, DCAP, MCAP, KCAP = 128, 64, 32, 4096
 S = 0x5eed
@@ -70,65 +71,9 @@ def test_record_bytes_follow_the_documented_layout(built, cap, cn, dcap):
 
 # ------------------------------------------------------------------ GPU helpers
 
-def _slice(poses, lw, sm, sof, dm, dof, lo, hi):
-    so, do = sof[lo:hi + 1], dof[lo:hi + 1]
-    return (poses[lo:hi].copy(), lw[lo:hi].copy(), sm[so[0]:so[-1]].copy(), (so - so[0]).astype(np.int32),
-            dm[do[0]:do[-1]].copy(), (do - do[0]).astype(np.int32))
-
-
 def _load(f, poses, lw, sm, sof, dm, dof):
     f.load(poses, lw, sm, sof)
     f.load_dynamic(dm, dof)
-
-
-def _emulated_settle(shards, ctrl, k):
-    for sf in shards:
-        sf.poll()
-    for r, sf in enumerate(shards):  # point-to-point overflow transfers
-        for s_, buf in sf._ovf[1]:
-            src = [t for d, t in shards[s_]._ovf[0] if d == r]
-            assert len(src) == 1 and src[0].numel() == buf.numel()
-            buf.copy_(src[0])
-    for sf in shards:
-        sf.settle_finish(ctrl, k)
-
-
-def _emulated_step(shards, ctrl, k, dev):
-    """One sync-free sharded step (ShardedFilter.step) of every emulated rank,
-    the collectives emulated by device copies between the shards' buffers."""
-    import torch
-    for sf in shards:
-        sf.local_update(ctrl, k)
-    _emulated_settle(shards, ctrl, k)
-    for sf in shards:
-        if sf.aux is None:
-            sf.w_all.copy_(torch.cat([o.w_local for o in shards]))
-        else:  # the all-gather on the plan stream, after every rank's log-weights are final
-            for o in shards:
-                o.f.wait_logw(sf.aux.cuda_stream)
-            with torch.cuda.stream(sf.aux):
-                sf.w_all.copy_(torch.cat([o.w_local for o in shards]))
-        sf.plan(k)
-    blk = shards[0].K * shards[0].record_bytes
-    for d, sf in enumerate(shards):  # equal-split all_to_all: block d of every rank -> rank d
-        sf.recv_blocks.copy_(torch.cat([src.send_blocks[d * blk:(d + 1) * blk] for src in shards]))
-        sf.receive()
-
-
-def _gathered(filters):
-    """The ranks' stores in rank order as one (poses, lw, sm, sof, dm, dof)."""
-    got = [f.export() for f in filters]
-    dyn = [f.export_dynamic() for f in filters]
-
-    def cat_offs(parts):
-        o = [0]
-        for p in parts:
-            o.extend((np.asarray(p[1:]) + o[-1]).tolist())
-        return np.asarray(o, dtype=np.int32)
-
-    return (np.concatenate([g[0] for g in got]), np.concatenate([g[1] for g in got]),
-            np.concatenate([g[2] for g in got]), cat_offs([g[3] for g in got]),
-            np.concatenate([d[0] for d in dyn]), cat_offs([d[1] for d in dyn]))
 
 
 def _assert_same_particles(a, b, label):
@@ -157,7 +102,7 @@ def _sharded_vs_single(world, n, K, steps=3, ackerman=False, empty_steps=(), sub
     particle and 10 measurements; equal after every step.  after(shards): called
     on the settled shards after the last step.  Returns (pending, moved)."""
     import torch
-    from phdslam.dist import ShardedFilter
+    from phdslam.dist import LocalWorld, ShardedFilter
     N = world * n
     cfg = mixed_config(motionType=1 if ackerman else 0, resampleThresh=1.0, subdividePredict=subdivide)
     if ackerman:  # (the defaults leave the vehicle's geometry and its control noise zero)
@@ -173,8 +118,9 @@ def _sharded_vs_single(world, n, K, steps=3, ackerman=False, empty_steps=(), sub
     for r in range(world):
         f = _filter(cfg, n)
         f.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        _load(f, *_slice(poses, lw, sm, sof, dm, dof, r * n, (r + 1) * n))
+        _load(f, *slice_mixed(poses, lw, sm, sof, dm, dof, r * n, (r + 1) * n))
         shards.append(ShardedFilter(f, None, dev, world=world, rank=r, seed=S, block_records=K))
+    ranks = LocalWorld(shards)
     z_empty = z[:0]
     prev = None
     for k in range(1, steps + 1):
@@ -193,14 +139,14 @@ def _sharded_vs_single(world, n, K, steps=3, ackerman=False, empty_steps=(), sub
             single.resample(uniforms=None, step=k)
         for sf in shards:
             sf.f.set_measurements(zk)
-        _emulated_step(shards, ctrl, k, dev)
-        _emulated_settle(shards, None, None)  # as flush(): the store is final
+        ranks.step(ctrl, k)
+        ranks.flush()  # the store is final
         torch.cuda.synchronize()
         if k in empty_steps:  # (no update: no resample)
             assert not any(sf.last[1] for sf in shards)
         else:
             assert all(sf.last[1] for sf in shards)
-        prev = _gathered([sf.f for sf in shards])
+        prev = gathered_mixed([sf.f for sf in shards])
         _assert_same_particles((*single.export(), *single.export_dynamic()), prev, f"step {k}")
     pending = sum(sf.stats["pending_slots"] for sf in shards)
     moved = sum(sf.stats["migrated"] for sf in shards)
@@ -340,20 +286,6 @@ def test_readers_after_migration(gpu):
 
 # ------------------------------------------------------------------ 6. the C++ host
 
-class _LocalComm:
-    """The transport of a world-1 ShardedFilter: every collective is a copy."""
-
-    def all_gather(self, out, inp):
-        out.copy_(inp)
-
-    def all_to_all_equal(self, out, inp):
-        out.copy_(inp)
-
-    def exchange(self, sends, recvs):
-        for (_, t), (_, b) in zip(sends, recvs):
-            b.copy_(t)
-
-
 @pytest.mark.gpu
 def test_group_rank_matches_sharded_filter(gpu):
     """GroupRank (the C++ host's per-process rank, one C call per step) at world
@@ -361,7 +293,7 @@ def test_group_rank_matches_sharded_filter(gpu):
     store, bytes.  At world 1 the exchange is skipped, so this checks that the
     C++ host accepts the model and the record size, no more."""
     import torch
-    from phdslam.dist import GroupRank, ShardedFilter
+    from phdslam.dist import GroupRank, LocalWorld, ShardedFilter
     n, steps = 32, 3
     cfg = mixed_config(motionType=0, resampleThresh=1.0)
     poses, sm, sof, dm, dof, z = mixed_scenario(cfg, n, 30, 10, 10)
@@ -373,12 +305,13 @@ def test_group_rank_matches_sharded_filter(gpu):
         _load(f, poses, lw, sm, sof, dm, dof)
         f.set_measurements(z)
         if kind == "torch":
-            sf = ShardedFilter(f, None, dev, world=1, rank=0, block_records=4, comm=_LocalComm())
+            sf = ShardedFilter(f, None, dev, world=1, rank=0, block_records=4)
         else:
             sf = GroupRank(f, None, dev, world=1, rank=0, block_records=4)
+        run = LocalWorld([sf]) if kind == "torch" else sf
         for k in range(1, steps + 1):
-            sf.step(None, k)
-        sf.flush()
+            run.step(None, k)
+        run.flush()
         torch.cuda.synchronize()
         f.check_errors()
         out.append(((*f.export(), *f.export_dynamic()), dict(sf.stats)))

@@ -21,6 +21,7 @@ import pytest
 
 import parity
 import pyoracle
+from sharded_helpers import gathered_store, slice_store
 from phdslam.types import GAUSSIAN2D, MEASUREMENT, POSE
 
 pytestmark = pytest.mark.gpu
@@ -1076,47 +1077,8 @@ def test_step_fused_predict_equals_separate_kernels(gpu, cid):
         assert a.tobytes() == b.tobytes()
 
 
-def _slice_particles(poses, lw, maps, offs, lo, hi):
-    o = offs[lo:hi + 1]
-    return poses[lo:hi].copy(), lw[lo:hi].copy(), maps[o[0]:o[-1]].copy(), (o - o[0]).astype(np.int32)
-
-
-def _emulated_step(shards, ctrl, k, dev):
-    """One sync-free sharded step (ShardedFilter.step) of every emulated rank,
-    the collectives emulated by device copies between the shards' buffers."""
-    import torch
-    for sf in shards:
-        sf.local_update(ctrl, k)
-    _emulated_settle(shards, ctrl, k)
-    for sf in shards:
-        if sf.aux is None:
-            sf.w_all.copy_(torch.cat([o.w_local for o in shards]))
-        else:  # the all-gather beside part C, as ShardedFilter.gather: after every rank's log-weights are final
-            for o in shards:
-                o.f.wait_logw(sf.aux.cuda_stream)
-            with torch.cuda.stream(sf.aux):
-                sf.w_all.copy_(torch.cat([o.w_local for o in shards]))
-        sf.plan(k)
-    blk = shards[0].K * shards[0].record_bytes
-    for d, sf in enumerate(shards):  # equal-split all_to_all: block d of every rank -> rank d
-        sf.recv_blocks.copy_(torch.cat([src.send_blocks[d * blk:(d + 1) * blk] for src in shards]))
-        sf.receive()
-
-
-def _emulated_settle(shards, ctrl, k):
-    for sf in shards:
-        sf.poll()
-    for r, sf in enumerate(shards):  # point-to-point overflow transfers
-        for s_, buf in sf._ovf[1]:
-            src = [t for d, t in shards[s_]._ovf[0] if d == r]
-            assert len(src) == 1 and src[0].numel() == buf.numel()
-            buf.copy_(src[0])
-    for sf in shards:
-        sf.settle_finish(ctrl, k)
-
-
 def _sharded_vs_single(cid, world, n, K, G=32, M=16, steps=3, caps=None, S=0x5eed, births=False, empty_steps=()):
-    """`world` emulated ranks of ShardedFilter (sync-free: global normalise /
+    """`world` ranks of ShardedFilter under LocalWorld (sync-free: global normalise /
     resample on the gathered log-weights, fixed blocks of K records per peer, the
     rest exchanged after the next update is enqueued and its slots re-updated)
     on one device against a single context of world * n particles stepped from
@@ -1133,7 +1095,7 @@ def _sharded_vs_single(cid, world, n, K, G=32, M=16, steps=3, caps=None, S=0x5ee
     Returns (pending slots, migrated particles) over the run."""
     import torch
     import phdslam
-    from phdslam.dist import ShardedFilter
+    from phdslam.dist import LocalWorld, ShardedFilter
     caps = caps or {}
     N = world * n
     c, poses, lw, maps, offs, z = phdslam.config_scenario(cid, n=N, G=G, M=M)
@@ -1153,19 +1115,11 @@ def _sharded_vs_single(cid, world, n, K, G=32, M=16, steps=3, caps=None, S=0x5ee
         f.set_seed(S)
         f.set_step_births(1 if births else 0)
         f.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        f.load(*_slice_particles(poses, lw, maps, offs, r * n, (r + 1) * n))
+        f.load(*slice_store((poses, lw, maps, offs), r * n, (r + 1) * n))
         if not births:  # (with births the scan is set before every step: its previous one from step 2 on)
             f.set_measurements(z)
         shards.append(ShardedFilter(f, None, dev, world=world, rank=r, seed=S, block_records=K))
-
-    def gathered():
-        got = [sf.f.export() for sf in shards]
-        gmaps, goffs = [], [0]
-        for g in got:
-            gmaps.append(g[2])
-            goffs.extend((np.asarray(g[3][1:]) + goffs[-1]).tolist())
-        return (np.concatenate([g[0] for g in got]), np.concatenate([g[1] for g in got]),
-                np.concatenate(gmaps), np.asarray(goffs, dtype=np.int32))
+    ranks = LocalWorld(shards)
 
     pending = 0
     z_empty = z[:0]
@@ -1192,10 +1146,10 @@ def _sharded_vs_single(cid, world, n, K, G=32, M=16, steps=3, caps=None, S=0x5ee
         if births or empty_steps:
             for sf in shards:
                 sf.f.set_measurements(zk)
-        _emulated_step(shards, ctrl, k, dev)
-        # the shards' state after step k: settle the open plan as flush() does
+        ranks.step(ctrl, k)
+        # the shards' state after step k: settle the open plan
         # (no update follows) — on copies of the contexts' store via export
-        _emulated_settle(shards, None, None)
+        ranks.flush()
         torch.cuda.synchronize()
         pending += sum(sf.stats["pending_slots"] for sf in shards)
         if k in empty_steps:  # (no update: no resample, main.cpp:1281-1297)
@@ -1205,7 +1159,7 @@ def _sharded_vs_single(cid, world, n, K, G=32, M=16, steps=3, caps=None, S=0x5ee
         moved = sum(sf.stats["migrated"] for sf in shards)
         records = sum(sf.stats["records"] for sf in shards)
         assert records <= moved
-        gathered_prev = gathered()
+        gathered_prev = gathered_store([sf.f for sf in shards])
         sp, sw, sm, so = single.export()
         gp, gw, gm, goffs = gathered_prev
         assert len(gp) == N
@@ -1300,20 +1254,6 @@ def test_sharded_step_config5_whole_job(gpu):
     assert moved > 0
 
 
-class _LocalComm:
-    """The transport of a world-1 ShardedFilter: every collective is a copy."""
-
-    def all_gather(self, out, inp):
-        out.copy_(inp)
-
-    def all_to_all_equal(self, out, inp):
-        out.copy_(inp)
-
-    def exchange(self, sends, recvs):
-        for (_, t), (_, b) in zip(sends, recvs):
-            b.copy_(t)
-
-
 @pytest.mark.parametrize("cid,n,steps", [(2, 256, 3), (3, 300, 2)])
 def test_group_driver_matches_sharded_filter(gpu, tmp_path, cid, n, steps):
     """The multi-GPU C++ host (phdslam_run --synth --gpus N over
@@ -1324,7 +1264,7 @@ def test_group_driver_matches_sharded_filter(gpu, tmp_path, cid, n, steps):
     import subprocess
     import torch
     import phdslam
-    from phdslam.dist import ShardedFilter
+    from phdslam.dist import LocalWorld, ShardedFilter
     from phdslam.scenario import SEED_BASE, bench_capacities
     exe = os.path.join(REPO, "cuda-phdslam_amd", "phdslam", "phdslam_run")
     dump = tmp_path / "group.bin"
@@ -1340,7 +1280,7 @@ def test_group_driver_matches_sharded_filter(gpu, tmp_path, cid, n, steps):
     f.load(poses, lw, maps, offs)
     f.set_measurements(z)
     f.set_check_each_update(False)
-    sf = ShardedFilter(f, None, dev, world=1, rank=0, block_records=4, comm=_LocalComm())
+    sf = LocalWorld([ShardedFilter(f, None, dev, world=1, rank=0, block_records=4)])
     ctrl = (2.0, 0.05) if c.motionType == 1 else None
     for k in range(1, steps + 1):
         sf.step(ctrl, k)
@@ -1378,7 +1318,7 @@ def test_group_rank_matches_sharded_filter(gpu, cid, n, steps):
     step counters agree."""
     import torch
     import phdslam
-    from phdslam.dist import GroupRank, ShardedFilter
+    from phdslam.dist import GroupRank, LocalWorld, ShardedFilter
     from phdslam.scenario import SEED_BASE, bench_capacities
     cfg, _, G, M, _ = phdslam.preset(cid)
     c, poses, lw, maps, offs, z = phdslam.config_scenario(cid, n=n)
@@ -1393,12 +1333,13 @@ def test_group_rank_matches_sharded_filter(gpu, cid, n, steps):
         f.set_measurements(z)
         f.set_check_each_update(False)
         if kind == "torch":
-            sf = ShardedFilter(f, None, dev, world=1, rank=0, block_records=4, comm=_LocalComm())
+            sf = ShardedFilter(f, None, dev, world=1, rank=0, block_records=4)
         else:
             sf = GroupRank(f, None, dev, world=1, rank=0, block_records=4)
+        run = LocalWorld([sf]) if kind == "torch" else sf
         for k in range(1, steps + 1):
-            sf.step(ctrl, k)
-        sf.flush()
+            run.step(ctrl, k)
+        run.flush()
         torch.cuda.synchronize()
         f.check_errors()
         out.append((f.export(), dict(sf.stats)))
@@ -1496,7 +1437,7 @@ def test_sharded_step_overflow_recovery_reupdates_slots(gpu, K):
     without the blocks equal each other exactly."""
     import torch
     import phdslam
-    from phdslam.dist import ShardedFilter
+    from phdslam.dist import LocalWorld, ShardedFilter
     world, n = 3, 64
     c, poses, lw, maps, offs, z = phdslam.config_scenario(2, n=world * n, G=32, M=16)
     c.resampleThresh = 1.0
@@ -1508,12 +1449,13 @@ def test_sharded_step_overflow_recovery_reupdates_slots(gpu, K):
             f = _filter(c, n)
             f.set_seed(7)
             f.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-            f.load(*_slice_particles(poses, lw, maps, offs, r * n, (r + 1) * n))
+            f.load(*slice_store((poses, lw, maps, offs), r * n, (r + 1) * n))
             f.set_measurements(z)
             shards.append(ShardedFilter(f, None, dev, world=world, rank=r, seed=7, block_records=kk))
+        ranks = LocalWorld(shards)
         for k in range(1, 4):
-            _emulated_step(shards, (2.0, 0.05), k, dev)
-        _emulated_settle(shards, None, None)
+            ranks.step((2.0, 0.05), k)
+        ranks.flush()
         torch.cuda.synchronize()
         runs.append([sf.f.export() for sf in shards])
         if kk == 0:

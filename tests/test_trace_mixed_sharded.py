@@ -10,8 +10,8 @@ phd_step; and tracing leaves the particles as an untraced run leaves them.
 tests/test_trace_mixed.py holds the single context's records to the
 synchronous entry points.
 
-Emulated ranks on one device, the collectives as device copies (the pattern of
-tests/test_trace_sharded.py and tests/test_gpu_mixed_sharded.py).  Three runs
+Emulated ranks on one device, the collectives as device copies
+(phdslam.dist.LocalWorld).  Three runs
 per case share a scenario: a settled run (every step's plan settled and the
 shards exported: the state the single context is loaded from before each
 scan), the free-running untraced run and the free-running traced run.  Every
@@ -37,7 +37,8 @@ import functools
 import numpy as np
 import pytest
 
-from test_gpu_mixed_sharded import _LocalComm, _emulated_settle, _gathered, _load, _slice
+from sharded_helpers import gathered_mixed, slice_mixed
+from test_gpu_mixed_sharded import _load
 from test_trace_sharded import _exported
 
 CAP, DCAP, MCAP, KCAP = 128, 64, 32, 4096
@@ -129,40 +130,19 @@ def _spy_polls(sf):
     sf.f.shard_poll = spy
 
 
-def _emulated_step(shards, ctrl, k):
-    """ShardedFilter.step of every emulated rank (tests/test_trace_sharded.py).
-    Returns the gathered trace blocks as int32 rows (None untraced); every
-    rank's sf.polled holds what its poll of the previous step's plan returned
-    (None: no plan was open)."""
+def _step(ranks, ctrl, k):
+    """LocalWorld.step.  Returns the gathered trace blocks as int32 rows (None
+    untraced), read from rank 0's buffer after the step; every rank's sf.polled
+    holds what its poll of the previous step's plan returned (None: no plan was
+    open)."""
     import torch
+    shards = ranks.shards
     for sf in shards:
         sf.polled = None
-        sf.local_update(ctrl, k)
-    _emulated_settle(shards, ctrl, k)
-    for sf in shards:
-        if sf.aux is None:
-            sf.w_all.copy_(torch.cat([o.w_local for o in shards]))
-        else:  # beside part C, as ShardedFilter.gather: after every rank's log-weights are final
-            for o in shards:
-                o.f.wait_logw(sf.aux.cuda_stream)
-            with torch.cuda.stream(sf.aux):
-                sf.w_all.copy_(torch.cat([o.w_local for o in shards]))
-    blocks = None
-    if shards[0].trace_block is not None:
-        for sf in shards:
-            sf.trace_pack(k)
-        cat = torch.cat([sf.trace_block for sf in shards])
-        for sf in shards:
-            sf.trace_blocks.copy_(cat)
-            sf.trace_append()
-        blocks = cat.view(torch.int32).view(len(shards), -1)
-    for sf in shards:
-        sf.plan(k)
-    blk = shards[0].K * shards[0].record_bytes
-    for d, sf in enumerate(shards):  # equal-split all_to_all: block d of every rank -> rank d
-        sf.recv_blocks.copy_(torch.cat([src.send_blocks[d * blk:(d + 1) * blk] for src in shards]))
-        sf.receive()
-    return blocks
+    ranks.step(ctrl, k)
+    if shards[0].trace_block is None:
+        return None
+    return shards[0].trace_blocks.view(torch.int32).view(len(shards), -1)
 
 
 def _sharded_run(cfg, state, zsets, world, n, K, trace=None, settled=False, toggle=False, weights=None, **cap):
@@ -179,7 +159,7 @@ def _sharded_run(cfg, state, zsets, world, n, K, trace=None, settled=False, togg
     previous step's plan — the last received[r] slots of rank r name the sets X
     until the next update), decisions, pending."""
     import torch
-    from phdslam.dist import ShardedFilter
+    from phdslam.dist import LocalWorld, ShardedFilter
     dev = torch.device("cuda", 0)
     ctrl = _control(cfg)
     weights = weights or {}
@@ -187,7 +167,7 @@ def _sharded_run(cfg, state, zsets, world, n, K, trace=None, settled=False, togg
     for r in range(world):
         f = _filter(cfg, n, **cap)
         f.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        _load(f, *_slice(*state, r * n, (r + 1) * n))
+        _load(f, *slice_mixed(*state, r * n, (r + 1) * n))
         sf = ShardedFilter(f, None, dev, world=world, rank=r, seed=S, block_records=K)
         _spy_polls(sf)
         if toggle:
@@ -197,6 +177,7 @@ def _sharded_run(cfg, state, zsets, world, n, K, trace=None, settled=False, togg
         if trace:
             sf.enable_trace_mixed(*trace)
         shards.append(sf)
+    ranks = LocalWorld(shards)
     out = dict(states=[], decisions=[], headers=[], received=[])
     keep = []  # (the device tensors the ranks' log-weights were set from)
 
@@ -212,7 +193,7 @@ def _sharded_run(cfg, state, zsets, world, n, K, trace=None, settled=False, togg
     def settle_now():
         for sf in shards:
             sf.polled = None
-        _emulated_settle(shards, None, None)
+        ranks.flush()
         torch.cuda.synchronize()
         return polled()
 
@@ -220,7 +201,7 @@ def _sharded_run(cfg, state, zsets, world, n, K, trace=None, settled=False, togg
     for k, zk in enumerate(zsets, start=1):
         for sf in shards:
             sf.f.set_measurements(zk)
-        blocks = _emulated_step(shards, ctrl, k)
+        blocks = _step(ranks, ctrl, k)
         got = polled()
         out["received"].append(early if early is not None else got if got is not None else [0] * world)
         early = None
@@ -236,7 +217,7 @@ def _sharded_run(cfg, state, zsets, world, n, K, trace=None, settled=False, togg
                 sf.f.set_log_weights_from(keep[-1].data_ptr())
             torch.cuda.synchronize()
         if settled:
-            out["states"].append(_gathered([sf.f for sf in shards]))
+            out["states"].append(gathered_mixed([sf.f for sf in shards]))
     if early is None:
         settle_now()
     torch.cuda.synchronize()
@@ -499,7 +480,7 @@ def test_dynamic_map_size_edges(gpu, size):
     for r in range(world):
         f = _filter(cfg, n, **kw)
         f.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        _load(f, *_slice(*state, r * n, (r + 1) * n))
+        _load(f, *slice_mixed(*state, r * n, (r + 1) * n))
         f.set_measurements(none)
         ranks.append(f)
     torch.cuda.synchronize()
@@ -538,7 +519,7 @@ def test_dynamic_map_size_edges(gpu, size):
         want = dm[dof[best]:dof[best + 1]]
         assert _bits(dmaps[0][:rows]) == _bits(want[:rows]) and not np.any(dmaps[0][rows:].view(np.uint8))
     for r, f in enumerate(ranks):  # the stores are exported as loaded
-        want = _slice(*state, r * n, (r + 1) * n)
+        want = slice_mixed(*state, r * n, (r + 1) * n)
         for x, y in zip((*f.export(), *f.export_dynamic()), want):
             assert _bits(x) == _bits(y)
         f.close()
@@ -587,7 +568,7 @@ def test_group_rank_trace_matches_sharded_filter(gpu):
     through RCCL at world 1 against a world-1 ShardedFilter and the single
     context's traced phd_step chain: one step sequence each."""
     import torch
-    from phdslam.dist import GroupRank, ShardedFilter
+    from phdslam.dist import GroupRank, LocalWorld, ShardedFilter
     n, steps = 32, 4
     cfg = _config(1.0)
     state, z = _scenario(cfg, n)
@@ -603,13 +584,14 @@ def test_group_rank_trace_matches_sharded_filter(gpu):
                 f.step(None, do_predict=True, step=k, readback=False)
         else:
             if kind == "torch":
-                sf = ShardedFilter(f, None, dev, world=1, rank=0, seed=S, block_records=4, comm=_LocalComm())
+                sf = ShardedFilter(f, None, dev, world=1, rank=0, seed=S, block_records=4)
             else:
                 sf = GroupRank(f, None, dev, world=1, rank=0, seed=S, block_records=4)
             sf.enable_trace_mixed(steps, SNAP, DSNAP)
+            run = LocalWorld([sf]) if kind == "torch" else sf
             for k in range(1, steps + 1):
-                sf.step(None, k)
-            sf.flush()
+                run.step(None, k)
+            run.flush()
             torch.cuda.synchronize()
         assert f.trace_count() == steps
         got[kind] = (*f.read_trace()[:2], *f.read_trace_dynamic())

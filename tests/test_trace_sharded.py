@@ -6,8 +6,8 @@ the record a single context of N = world * n particles (the shards' particles
 in rank order) writes for that scan in a traced phd_step.  tests/test_trace.py
 holds the single context's record to the synchronous entry points.
 
-Emulated ranks on one device, the collectives as device copies (the pattern of
-tests/test_gpu_parity.py::_emulated_step).  Three runs per case share a
+Emulated ranks on one device, the collectives as device copies
+(phdslam.dist.LocalWorld).  Three runs per case share a
 scenario: a settled run (every step's plan settled and the shards exported: the
 state the single context is loaded from before each scan), the free-running
 untraced run and the free-running traced run.  Small synthetic scenarios as
@@ -20,6 +20,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+from sharded_helpers import gathered_store, slice_store
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -91,65 +93,13 @@ def _filter(c, n, **kw):
     return f
 
 
-def _slice(state, lo, hi):
-    poses, lw, maps, offs = state
-    o = offs[lo:hi + 1]
-    return poses[lo:hi].copy(), lw[lo:hi].copy(), maps[o[0]:o[-1]].copy(), (o - o[0]).astype(np.int32)
-
-
-def _emulated_settle(shards, ctrl, k):
-    for sf in shards:
-        sf.poll()
-    for r, sf in enumerate(shards):  # point-to-point overflow transfers
-        for s_, buf in sf._ovf[1]:
-            src = [t for d, t in shards[s_]._ovf[0] if d == r]
-            assert len(src) == 1 and src[0].numel() == buf.numel()
-            buf.copy_(src[0])
-    for sf in shards:
-        sf.settle_finish(ctrl, k)
-
-
-def _emulated_step(shards, ctrl, k):
-    """ShardedFilter.step of every emulated rank: the all-gathers as torch.cat of
-    the shards' buffers, the all-to-all as copies of the blocks.  Returns the
-    rank whose trace block carries the owner flag (None untraced)."""
+def _owners(shards):
+    """Per rank, the owner flag of its trace block (None untraced), read from
+    rank 0's gathered blocks after the step."""
     import torch
-    for sf in shards:
-        sf.local_update(ctrl, k)
-    _emulated_settle(shards, ctrl, k)
-    for sf in shards:
-        if sf.aux is None:
-            sf.w_all.copy_(torch.cat([o.w_local for o in shards]))
-        else:  # beside part C, as ShardedFilter.gather: after every rank's log-weights are final
-            for o in shards:
-                o.f.wait_logw(sf.aux.cuda_stream)
-            with torch.cuda.stream(sf.aux):
-                sf.w_all.copy_(torch.cat([o.w_local for o in shards]))
-    owners = None
-    if shards[0].trace_block is not None:
-        for sf in shards:
-            sf.trace_pack(k)
-        blocks = torch.cat([sf.trace_block for sf in shards])
-        for sf in shards:
-            sf.trace_blocks.copy_(blocks)
-            sf.trace_append()
-        owners = blocks.view(torch.int32).view(len(shards), -1)[:, 1]  # TRACE_BH_OWNER
-    for sf in shards:
-        sf.plan(k)
-    blk = shards[0].K * shards[0].record_bytes
-    for d, sf in enumerate(shards):  # equal-split all_to_all: block d of every rank -> rank d
-        sf.recv_blocks.copy_(torch.cat([src.send_blocks[d * blk:(d + 1) * blk] for src in shards]))
-        sf.receive()
-    return owners
-
-
-def _gathered(shards):
-    got = [sf.f.export() for sf in shards]
-    offs = [0]
-    for g in got:
-        offs.extend((np.asarray(g[3][1:]) + offs[-1]).tolist())
-    return (np.concatenate([g[0] for g in got]), np.concatenate([g[1] for g in got]),
-            np.concatenate([g[2] for g in got]), np.asarray(offs, dtype=np.int32))
+    if shards[0].trace_block is None:
+        return None
+    return shards[0].trace_blocks.view(torch.int32).view(len(shards), -1)[:, 1]  # TRACE_BH_OWNER
 
 
 def _sharded_run(c, state, zsets, world, n, K, trace=None, settled=False, toggle=False, errors=False, **cap):
@@ -162,14 +112,14 @@ def _sharded_run(c, state, zsets, world, n, K, trace=None, settled=False, toggle
     errors (per scan, the ranks' status_errors() summed, with errors=True),
     pending (slots re-updated after their record arrived, over the run)."""
     import torch
-    from phdslam.dist import ShardedFilter
+    from phdslam.dist import LocalWorld, ShardedFilter
     dev = torch.device("cuda", 0)
     ctrl = _control(c)
     shards = []
     for r in range(world):
         f = _filter(c, n, **cap)
         f.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        f.load(*_slice(state, r * n, (r + 1) * n))
+        f.load(*slice_store(state, r * n, (r + 1) * n))
         sf = ShardedFilter(f, None, dev, world=world, rank=r, seed=FILTER_SEED, block_records=K)
         if toggle:
             sf.enable_trace(8)
@@ -177,24 +127,26 @@ def _sharded_run(c, state, zsets, world, n, K, trace=None, settled=False, toggle
         if trace:
             sf.enable_trace(*trace)
         shards.append(sf)
+    ranks = LocalWorld(shards)
     out = dict(states=[], decisions=[], owners=[], errors=[])
     for k, zk in enumerate(zsets, start=1):
         for sf in shards:
             sf.f.set_measurements(zk)
-        owners = _emulated_step(shards, ctrl, k)
+        ranks.step(ctrl, k)
+        owners = _owners(shards)
         if owners is not None:
             out["owners"].append(owners.cpu().numpy().copy())
         if settled:
-            _emulated_settle(shards, None, None)
+            ranks.flush()
             torch.cuda.synchronize()
-            out["states"].append(_gathered(shards))
+            out["states"].append(gathered_store([sf.f for sf in shards]))
         if errors:
             out["errors"].append(sum(sf.f.status_errors() for sf in shards))
         if k > 1 or settled:  # the plan of step k-1 was polled inside step k (settled: step k's, just now)
             assert len(set(sf.last[1] for sf in shards)) == 1
             out["decisions"].append(int(shards[0].last[1]))
     if not settled:
-        _emulated_settle(shards, None, None)
+        ranks.flush()
         out["decisions"].append(int(shards[0].last[1]))
     torch.cuda.synchronize()
     out["pending"] = sum(sf.stats["pending_slots"] for sf in shards)
@@ -329,7 +281,7 @@ def test_card_dist_with_expected_map_estimate_is_refused(gpu):
     from phdslam.dist import ShardedFilter
     c, state, z = _scenario(3, 16, map_estimate=2)
     f = _filter(c, 8)
-    f.load(*_slice(state, 0, 8))
+    f.load(*slice_store(state, 0, 8))
     sf = ShardedFilter(f, None, torch.device("cuda", 0), world=2, rank=0, block_records=2)
     with pytest.raises(phdslam.PHDError) as e:
         sf.enable_trace(4, card_dist=True)
@@ -372,20 +324,6 @@ def test_off_means_off(gpu):
             assert _bits(x) == _bits(y)
 
 
-class _LocalComm:
-    """The transport of a world-1 ShardedFilter: every collective is a copy."""
-
-    def all_gather(self, out, inp):
-        out.copy_(inp)
-
-    def all_to_all_equal(self, out, inp):
-        out.copy_(inp)
-
-    def exchange(self, sends, recvs):
-        for (_, t), (_, b) in zip(sends, recvs):
-            b.copy_(t)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("cid", [2, 3])
 def test_group_rank_trace_matches_sharded_filter(gpu, cid):
@@ -393,7 +331,7 @@ def test_group_rank_trace_matches_sharded_filter(gpu, cid):
     the blocks, append inside phd_group_step) through RCCL at world 1 against a
     world-1 ShardedFilter and the single context's traced phd_step chain."""
     import torch
-    from phdslam.dist import GroupRank, ShardedFilter
+    from phdslam.dist import GroupRank, LocalWorld, ShardedFilter
     n, steps = 300, 4
     c, state, z = _scenario(cid, n)
     dev = torch.device("cuda", 0)
@@ -409,13 +347,14 @@ def test_group_rank_trace_matches_sharded_filter(gpu, cid):
                 f.step(ctrl, do_predict=True, step=k, readback=False)
         else:
             if kind == "torch":
-                sf = ShardedFilter(f, None, dev, world=1, rank=0, seed=FILTER_SEED, block_records=4, comm=_LocalComm())
+                sf = ShardedFilter(f, None, dev, world=1, rank=0, seed=FILTER_SEED, block_records=4)
             else:
                 sf = GroupRank(f, None, dev, world=1, rank=0, seed=FILTER_SEED, block_records=4)
             sf.enable_trace(steps)
+            run = LocalWorld([sf]) if kind == "torch" else sf
             for k in range(1, steps + 1):
-                sf.step(ctrl, k)
-            sf.flush()
+                run.step(ctrl, k)
+            run.flush()
             torch.cuda.synchronize()
         assert f.trace_count() == steps
         recs[kind] = f.read_trace()
