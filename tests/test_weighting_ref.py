@@ -231,8 +231,9 @@ if __name__ == "__main__":
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "oracle"))
     if "--tie" in sys.argv:
         print("TIE_SEED_STEP =", _find_tie_pairs())
+    import shard_plan_cases as SC  # the gathered sizes of the sharded plan (tests/test_gpu_shard_plan.py)
     print("D_ORACLE = {")
-    for case in C.CASES:
+    for case in C.CASES + SC.WCASES:
         _, d_w, d_neff = oracle_figures(case)
         print(f'    "{C.key(case)}": dict(lognorm={C.round_up(d_w):.2g}, neff={C.round_up(d_neff):.2g}),')
     print("}")

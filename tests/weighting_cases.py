@@ -68,6 +68,8 @@ def weights(dist, n, seed=3):
             w[0] = -8.0
     elif dist == "wide":
         w = rng.normal(0, 30, n).astype(np.float32)
+    elif dist == "sparse":  # `normal` on every eighth entry: an eighth of the CDF's steps, so of the near strata
+        w[np.arange(n) % 8 != 0] = -np.inf
     elif dist == "shifted":
         w = (w - np.float32(3e4)).astype(np.float32)
     elif dist == "tie":  # two exactly equal maxima, neither the last entry's neighbour
@@ -287,4 +289,66 @@ D_ORACLE = {
     "step-cphd-4097-holes": dict(lognorm=0, neff=7.2e-07),
     "step-split-4097-normal": dict(lognorm=0, neff=2.6e-07),
     "step-split-4097-two_far": dict(lognorm=0, neff=4.6e-07),
+    # the gathered sizes of the sharded plan (tests/shard_plan_cases.py)
+    "shard-phd-15-flat": dict(lognorm=0, neff=1.2e-07),
+    "shard-phd-15-holes": dict(lognorm=0, neff=5.2e-08),
+    "shard-phd-15-normal": dict(lognorm=0, neff=6.6e-08),
+    "shard-phd-15-one": dict(lognorm=0, neff=5.3e-08),
+    "shard-phd-15-two_far": dict(lognorm=0, neff=2.5e-08),
+    "shard-phd-15-wide": dict(lognorm=0, neff=2.6e-06),
+    "shard-phd-16-normal": dict(lognorm=0, neff=1.9e-07),
+    "shard-phd-16-one": dict(lognorm=0, neff=0),
+    "shard-phd-16-two_far": dict(lognorm=0, neff=9.8e-10),
+    "shard-phd-32-normal": dict(lognorm=0, neff=1.6e-07),
+    "shard-phd-32-one": dict(lognorm=0, neff=0),
+    "shard-phd-32-two_far": dict(lognorm=0, neff=9.8e-10),
+    "shard-phd-64-normal": dict(lognorm=0, neff=1.5e-07),
+    "shard-phd-1000-tie": dict(lognorm=0, neff=3.9e-07),
+    "shard-phd-1023-normal": dict(lognorm=0, neff=2.5e-07),
+    "shard-phd-1023-two_far": dict(lognorm=0, neff=5.5e-09),
+    "shard-phd-1024-normal": dict(lognorm=0, neff=7.6e-08),
+    "shard-phd-1024-two_far": dict(lognorm=0, neff=9.8e-10),
+    "shard-phd-1025-flat": dict(lognorm=0, neff=4.5e-16),
+    "shard-phd-1025-holes": dict(lognorm=0, neff=1.1e-07),
+    "shard-phd-1025-normal": dict(lognorm=0, neff=1.6e-07),
+    "shard-phd-1025-one": dict(lognorm=0, neff=9.4e-10),
+    "shard-phd-1025-two_far": dict(lognorm=0, neff=1.6e-08),
+    "shard-phd-1025-wide": dict(lognorm=8.1e-09, neff=6.8e-06),
+    "shard-phd-1105-flat": dict(lognorm=0, neff=3.6e-07),
+    "shard-phd-1105-holes": dict(lognorm=0, neff=2.2e-08),
+    "shard-phd-1105-normal": dict(lognorm=0, neff=1.5e-07),
+    "shard-phd-1105-one": dict(lognorm=0, neff=4.8e-09),
+    "shard-phd-1105-two_far": dict(lognorm=0, neff=2e-08),
+    "shard-phd-1105-wide": dict(lognorm=1.1e-08, neff=7.6e-06),
+    "shard-phd-2048-holes": dict(lognorm=0, neff=3.4e-08),
+    "shard-phd-2048-normal": dict(lognorm=0, neff=2.6e-07),
+    "shard-phd-2048-one": dict(lognorm=0, neff=0),
+    "shard-phd-2048-two_far": dict(lognorm=0, neff=9.8e-10),
+    "shard-phd-2049-tie": dict(lognorm=0, neff=3e-07),
+    "shard-phd-2112-holes": dict(lognorm=0, neff=3e-07),
+    "shard-phd-2112-normal": dict(lognorm=0, neff=2.8e-07),
+    "shard-phd-2112-one": dict(lognorm=0, neff=3e-08),
+    "shard-phd-2112-two_far": dict(lognorm=0, neff=1.1e-08),
+    "shard-phd-3072-holes": dict(lognorm=0, neff=8.5e-08),
+    "shard-phd-3072-normal": dict(lognorm=0, neff=6e-07),
+    "shard-phd-3072-one": dict(lognorm=0, neff=3e-08),
+    "shard-phd-3072-two_far": dict(lognorm=0, neff=9.8e-10),
+    "shard-phd-4096-holes": dict(lognorm=0, neff=5.2e-07),
+    "shard-phd-4096-normal": dict(lognorm=0, neff=5.1e-07),
+    "shard-phd-4096-two_far": dict(lognorm=0, neff=9.8e-10),
+    "shard-phd-4097-tie": dict(lognorm=0, neff=5.7e-07),
+    "shard-phd-4100-flat": dict(lognorm=0, neff=9e-07),
+    "shard-phd-4100-holes": dict(lognorm=0, neff=2.5e-07),
+    "shard-phd-4100-normal": dict(lognorm=0, neff=3.1e-07),
+    "shard-phd-4100-one": dict(lognorm=0, neff=9.4e-10),
+    "shard-phd-4100-two_far": dict(lognorm=0, neff=1.6e-08),
+    "shard-phd-4100-wide": dict(lognorm=5.4e-09, neff=6.2e-06),
+    "shard-phd-131072-one": dict(lognorm=0, neff=0),
+    "shard-phd-131072-sparse": dict(lognorm=0, neff=9.7e-08),
+    "shard-phd-131072-two_far": dict(lognorm=0, neff=9.8e-10),
+    "shard-phd-132096-one": dict(lognorm=0, neff=3.8e-09),
+    "shard-phd-132096-sparse": dict(lognorm=0, neff=4.6e-08),
+    "shard-phd-132096-two_far": dict(lognorm=0, neff=9.8e-10),
+    "shard-phd-263168-sparse": dict(lognorm=0, neff=9.3e-08),
+    "shard-phd-263168-two_far": dict(lognorm=0, neff=1.8e-08),
 }
