@@ -89,7 +89,8 @@ int phd_expected_map_dynamic(phd_ctx* ctx, phd_gaussian4d* out, long out_cap, lo
     const long nout = mixed_expected_map_dynamic(ctx->stream, ctx->st.d_src, ctx->mx.d_dmap[ctx->mx.dcur],
                                                  ctx->mx.d_dsize[ctx->mx.dcur], ctx->mx.d_dmap_x, ctx->mx.d_dsize_x,
                                                  ctx->n, ctx->mx.dcap, ctx->st.d_logw,
-                                                 ctx->cfg.minSeparation, out, out ? out_cap : 0, err);
+                                                 ctx->cfg.minSeparation, out, out ? out_cap : 0, ctx->eap4_mode,
+                                                 &ctx->eap4_rounds, &ctx->eap4_cells, err);
     if (nout < 0) return fail(PHD_E_HIP, "dynamic expected map: " + err);
     *n_out = nout;
     if (nout > 0 && (!out || nout > out_cap))
@@ -100,6 +101,19 @@ int phd_expected_map_dynamic(phd_ctx* ctx, phd_gaussian4d* out, long out_cap, lo
 int phd_expected_map_groups(phd_ctx* ctx, int* groups) {
     if (!ctx || !groups) return fail(PHD_E_ARG, "null argument");
     *groups = ctx->eap_groups;
+    return PHD_OK;
+}
+
+int phd_expected_map_dynamic_groups(phd_ctx* ctx, int* rounds, int* cells) {
+    if (!ctx || !rounds || !cells) return fail(PHD_E_ARG, "null argument");
+    *rounds = ctx->eap4_rounds;
+    *cells = ctx->eap4_cells;
+    return PHD_OK;
+}
+
+int phd_set_expected_map_dynamic_mode(phd_ctx* ctx, int mode) {
+    if (!ctx || (mode != 0 && mode != 1)) return fail(PHD_E_ARG, "bad arguments to phd_set_expected_map_dynamic_mode");
+    ctx->eap4_mode = mode;
     return PHD_OK;
 }
 
@@ -246,7 +260,8 @@ int phd_expected_map_dynamic_blocks(phd_ctx* ctx, const void* dev_blocks, int wo
     if (rc) return rc;
     std::string err;
     const long nout = mixed_expected_map_dynamic_blocks(&ctx->eap4, ctx->stream, dev_blocks, world, ctx->n, K_max,
-                                                        ctx->cfg.minSeparation, out, out ? out_cap : 0, err);
+                                                        ctx->cfg.minSeparation, out, out ? out_cap : 0, ctx->eap4_mode,
+                                                 &ctx->eap4_rounds, &ctx->eap4_cells, err);
     if (nout == -2) return fail(PHD_E_ARG, "phd_expected_map_dynamic_blocks: " + err);
     if (nout < 0) return fail(PHD_E_HIP, "dynamic expected map: " + err);
     *n_out = nout;

@@ -273,6 +273,8 @@ struct phd_ctx {
     phd::EapScratch* eap = nullptr;  // expected-map scratch (phd_eap.hip), allocated on first use
     int eap_groups = 0;
     phd::Eap4Scratch* eap4 = nullptr;  // the dynamic maps' blocks form (phd_mixed.hip), allocated on first use
+    int eap4_mode = 0;  // the dynamic expected map: 0 decision rounds, 1 the one workgroup only
+    int eap4_rounds = 0, eap4_cells = 0;  // of the last dynamic expected map (single or blocks form)
 
     /* waits for the context stream, then the members release (the stream last) */
     ~phd_ctx() {

@@ -582,5 +582,18 @@ void eap_launch_block_heads(hipStream_t st, const void* d_blocks, size_t stride_
 void eap_launch_concat(hipStream_t st, const void* d_blocks, size_t stride_words, int fields, int world, long K_max,
                        const int* d_off, long K, float* comp);
 std::string eap_refused_text(unsigned int refused);
+/* Stages of the reduce that do not depend on the component's dimension, shared
+ * with the dynamic maps' reduce (phd_mixed.hip; defined in phd_eap.hip): the
+ * identity, the lattice-cell key of every priority position (means in fields 1
+ * and 2 of a SoA of stride K), the 3 x 3 neighbour table of the occupied cells,
+ * the decision state scattered from cell order to position order, every
+ * position's seed key and seed flag, and the first index of every seed's group. */
+__global__ void k_iota_u32(unsigned int* a, long n);
+__global__ void k_eap_poskey(const float* comp, long K, const unsigned int* ord, float invR, unsigned long long* key,
+                             unsigned int* pos);
+__global__ void k_eap_nb9(const unsigned long long* cells, int ncell, int* nb9);
+__global__ void k_eap_state_pos(const int* state_t, const unsigned int* pos_by_cell, long K, int* state);
+__global__ void k_eap_seedkey(const int* state, long K, int* flag, unsigned int* key);
+__global__ void k_eap_gstart(const unsigned int* key_sorted, const int* slot, long K, int nseed, int* gstart);
 
 }  // namespace phd

@@ -39,6 +39,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 
@@ -512,8 +513,11 @@ hipError_t mixed_launch_predict_x(const int* slots, int count, const int* src, i
  * sort), seeds in that order absorb every unmerged later component at LLT
  * Mahalanobis distance < minSeparation (phd_eap_mahal4), the moments summed
  * serially in priority order by one lane (phd_eap4_*, the oracle's
- * expressions: orc_expected_map_dynamic) — one workgroup over the whole set
- * (dynamic maps are small: no benchmark config uses the mixed model). */
+ * expressions: orc_expected_map_dynamic).  Two forms of the greedy, the same
+ * bytes in the same order: decision rounds over the whole GPU (k_eap4_bound ..
+ * k_eap4_sum below: the static map's stages, phd_eap.hip, for 21-field
+ * components), and one workgroup over the whole set (k_eap4_merge: the
+ * fallback of inputs the lattice bound does not cover, and mode 1). */
 /* particle blockIdx.x's weighted components into the SoA comp (21 fields of
  * stride K) at its offset: the single context's gather and the sharded pack */
 __device__ __forceinline__ void eap4_gather_particle(const int* __restrict__ src, const float* __restrict__ dmap,
@@ -652,6 +656,253 @@ __global__ void __launch_bounds__(EAP4_NT) k_eap4_merge(const float* __restrict_
     if (tid == 0) *nout = count;
 }
 
+/* ---- the decision rounds: the static map's exact parallel greedy
+ * (phd_eap.hip, steps 2-6 of its header) for Gaussian4D components ----
+ * The lattice lies over the two position coordinates, cell side
+ * R = sqrt(1.05 T Λ), Λ the largest covariance trace of the set: a pair with
+ * phd_eap_mahal4 < T has |Δμ|² (all four coordinates, so the two of the
+ * position too) below 1.05 T (tr_a + tr_b) / 2 <= 1.05 T Λ (DESIGN.md §6,
+ * "Decision rounds": the bound for the float LLT as phd_eap_mahal4 states it, at any
+ * conditioning), so merge edges only join cells that touch. */
+
+/* the trace the bound, the records and the cull all use (one expression) */
+__device__ __forceinline__ float eap4_trace(float c00, float c11, float c22, float c33) {
+    return c00 + c11 + c22 + c33;
+}
+
+/* a positive variance below this (2^-60) leaves the range in which the bound's
+ * rounding argument holds (products of Cholesky entries may underflow) */
+#define EAP4_VAR_MIN 8.673617379884035e-19f
+
+/* The bound pass over a prepared SoA: Λ = the largest trace, as float bits
+ * (non-negative floats order as their bit patterns), and the flag of inputs
+ * the bound does not cover: a non-finite field (any of the 21), a negative
+ * variance (the trace would no longer bound the averaged one's row sums to a
+ * few ulps) or a positive variance below EAP4_VAR_MIN.  A finite covariance
+ * that is merely not positive definite is covered: its pairs' distance is NaN
+ * or infinite in every form, so they never merge. */
+__global__ void __launch_bounds__(256) k_eap4_bound(const float* __restrict__ comp, long K,
+                                                    unsigned int* __restrict__ lam_bits, int* __restrict__ bad) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    float tr = 0.f;
+    bool flag = false;
+    if (i < K) {
+        for (int f = 0; f < PHD_DYN_FIELDS; f++) flag |= !(fabsf(comp[(size_t)f * K + i]) < INFINITY);
+        float d[4];
+        for (int a = 0; a < 4; a++) {
+            d[a] = comp[(size_t)(5 + 5 * a) * K + i];
+            flag |= d[a] < 0.f || (d[a] > 0.f && d[a] < EAP4_VAR_MIN);
+        }
+        tr = eap4_trace(d[0], d[1], d[2], d[3]);
+        if (flag) tr = 0.f;
+    }
+    if (__ballot(flag) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, 1);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) tr = fmaxf(tr, __shfl_xor(tr, o, 64));
+    if ((threadIdx.x & 63) == 0 && tr > 0.f) atomicMax(lam_bits, __float_as_uint(tr));
+}
+
+/* Records in cell order t (pos_by_cell order), four planes of K float4 — what
+ * the decision rounds read, 16 words: (mean 0..3) | (trace, position bits,
+ * c00, c10) | (c20, c30, c11, c21) | (c31, c22, c32, c33): the lower triangle
+ * of the column-major covariance, all phd_eap_mahal4 reads. */
+__global__ void k_eap4_cellrec(const float* __restrict__ comp, long K, const unsigned int* __restrict__ ord,
+                               const unsigned int* __restrict__ pos_by_cell, float4* __restrict__ rec) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= K) return;
+    const unsigned int p = pos_by_cell[t];
+    const unsigned int i = ord[p];
+    auto c = [&](int k) { return comp[(size_t)(5 + k) * K + i]; };
+    rec[t] = make_float4(comp[1 * K + i], comp[2 * K + i], comp[3 * K + i], comp[4 * K + i]);
+    rec[K + t] = make_float4(eap4_trace(c(0), c(5), c(10), c(15)), __uint_as_float(p), c(0), c(1));
+    rec[2 * K + t] = make_float4(c(2), c(3), c(5), c(6));
+    rec[3 * K + t] = make_float4(c(7), c(10), c(11), c(15));
+}
+
+/* a record's planes as phd_eap_mahal4's arguments (it reads the lower triangle
+ * only; the upper entries are placeholders) */
+__device__ __forceinline__ void eap4_rec_args(const float4& r0, const float4& r1, const float4& r2, const float4& r3,
+                                              float* m, float* c) {
+    m[0] = r0.x, m[1] = r0.y, m[2] = r0.z, m[3] = r0.w;
+    c[0] = r1.z, c[1] = r1.w, c[2] = r2.x, c[3] = r2.y;
+    c[5] = r2.z, c[6] = r2.w, c[7] = r3.x;
+    c[10] = r3.y, c[11] = r3.z;
+    c[15] = r3.w;
+    c[4] = c[8] = c[9] = c[12] = c[13] = c[14] = 0.f;
+}
+
+#define EAP4R_NT 256 /* positions of a work item = records of a streamed tile */
+
+/* One synchronous decision round for one chunk of one occupied cell (work item
+ * = cell, first cell-order index, count; k_eap_lfmis's layout).  state[t]
+ * (cell order): -1 undecided, -2 seed, else the absorbing seed's position.
+ * Every thread owns one position j of the chunk and looks for its decider: the
+ * first higher-priority position k of the 3 x 3 cells (own cell first) that is
+ * not absorbed and has phd_eap_mahal4(k, j) < T — the seed is the first
+ * argument pair, as in k_eap4_merge.  The workgroup streams the nine cells'
+ * records through LDS in tiles of ascending position, entries already absorbed
+ * or past every thread's need compacted away, and stops at the first tile no
+ * thread still needs.  A pair passes the isotropic cull (|Δμ|² over all four
+ * coordinates below 1.05 T (tr_k + tr_j) / 2; a squared norm that overflowed
+ * is not culled) before the exact distance.  j becomes a seed with no decider,
+ * is absorbed when its decider is a seed, and otherwise waits for the next
+ * launch (counted): nothing here waits on another workgroup.  Decisions are
+ * final, so a state read in the same round only decides earlier. */
+__global__ void __launch_bounds__(EAP4R_NT)
+    k_eap4_lfmis(const int4* __restrict__ work, const float4* __restrict__ rec, long K, const int* __restrict__ nb9,
+                 const int* __restrict__ run, float T, int* state, int* __restrict__ pending) {
+    __shared__ float4 s_r[4][EAP4R_NT];
+    __shared__ int s_st[EAP4R_NT];
+    __shared__ int s_w[EAP4R_NT / 64], s_c[EAP4R_NT / 64];
+    const int4 wk = work[blockIdx.x];
+    const int c = wk.x, t = wk.y + threadIdx.x;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const bool own = (int)threadIdx.x < wk.z;
+    const bool undecided = own && __hip_atomic_load(state + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == -1;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 r0 = z4, r1 = z4, r2 = z4, r3 = z4;
+    if (undecided) {
+        r0 = rec[t];
+        r1 = rec[K + t];
+        r2 = rec[2 * K + t];
+        r3 = rec[3 * K + t];
+    }
+    float jm[4], jc[16];
+    eap4_rec_args(r0, r1, r2, r3, jm, jc);
+    const int pj = __float_as_int(r1.y);
+    int best = undecided ? pj : -1;  // the deciding position so far (pj: none); -1: nothing to find
+    int bst = 0;
+    const float thr = 1.05f * T * 0.5f;
+    for (int rr = 0; rr < 9; rr++) {
+        const int r = rr == 0 ? 4 : (rr <= 4 ? rr - 1 : rr);  // own cell first: its decider is usually there
+        const int cc = nb9[(size_t)c * 9 + r];
+        if (cc < 0) continue;
+        const int e1 = run[cc + 1];
+        for (int base = run[cc]; base < e1; base += EAP4R_NT) {
+            // the largest position any thread still accepts (block max; its barrier
+            // also retires the previous tile)
+            int v = best;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+            if (lane == 0) s_w[wid] = v;
+            __syncthreads();
+            int need = s_w[0];
+#pragma unroll
+            for (int w = 1; w < EAP4R_NT / 64; w++) need = max(need, s_w[w]);
+            const int tn = min(EAP4R_NT, e1 - base);
+            const int lead = __float_as_int(rec[K + base].y);
+            if (lead >= need) break;  // ascending positions: no later tile of this cell is needed either
+            // the tile's entries that can decide anyone: not absorbed, below `need`
+            // (compacted in position order)
+            float4 q1 = z4;
+            int sq = 0;
+            bool keep = false;
+            if ((int)threadIdx.x < tn) {
+                q1 = rec[K + base + threadIdx.x];
+                sq = __hip_atomic_load(state + base + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                keep = sq < 0 && __float_as_int(q1.y) < need;
+            }
+            const unsigned long long kb = __ballot(keep);
+            if (lane == 0) s_c[wid] = (int)__popcll(kb);
+            __syncthreads();
+            int off = 0, nk = 0;
+#pragma unroll
+            for (int w = 0; w < EAP4R_NT / 64; w++) {
+                off += w < wid ? s_c[w] : 0;
+                nk += s_c[w];
+            }
+            if (keep) {
+                off += (int)__popcll(kb & ((1ull << lane) - 1ull));
+                s_r[0][off] = rec[base + threadIdx.x];
+                s_r[1][off] = q1;
+                s_r[2][off] = rec[2 * K + base + threadIdx.x];
+                s_r[3][off] = rec[3 * K + base + threadIdx.x];
+                s_st[off] = sq;
+            }
+            __syncthreads();
+            for (int e = 0; e < nk && best >= 0; e++) {
+                const float4 e0 = s_r[0][e], e1v = s_r[1][e];
+                const int k = __float_as_int(e1v.y);
+                if (k >= best) break;
+                const float d0 = e0.x - r0.x, d1 = e0.y - r0.y, d2 = e0.z - r0.z, d3 = e0.w - r0.w;
+                const float n2 = d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+                if (n2 >= thr * (e1v.x + r1.x) && n2 < INFINITY) continue;
+                float km[4], kc[16];
+                eap4_rec_args(e0, e1v, s_r[2][e], s_r[3][e], km, kc);
+                if (phd_eap_mahal4(km, kc, jm, jc) < T) {
+                    best = k;
+                    bst = s_st[e];
+                    break;
+                }
+            }
+        }
+        __syncthreads();  // (the tile arrays and s_w are rewritten next)
+    }
+    bool wait = false;
+    if (undecided) {
+        if (best == pj || bst == -2) {
+            __hip_atomic_store(state + t, best == pj ? -2 : best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            wait = true;  // the first candidate seed is still undecided
+        }
+    }
+    const unsigned long long b = __ballot(wait);
+    if (lane == 0 && b != 0ull) atomicAdd(pending, (int)__popcll(b));
+}
+
+#define EAP4_PASS 64 /* members one LDS staging pass holds (one per lane) */
+
+/* Merged moments of seed g, one wave (a 64-thread workgroup) per seed: members
+ * mem[gstart[g] .. gstart[g + 1]) in priority order, the seed first.  The wave
+ * stages EAP4_PASS members at a time in LDS and lane 0 sums them serially with
+ * the shared phd_eap4_* functions in k_eap4_merge's order: the mean pass over
+ * the whole group, then the covariance pass.  Slot g is the seed's rank among
+ * the seeds in priority order, so out[] is in emission order. */
+__global__ void __launch_bounds__(64)
+    k_eap4_sum(const float* __restrict__ comp, long K, const unsigned int* __restrict__ ord,
+               const unsigned int* __restrict__ mem, const int* __restrict__ gstart,
+               phd_gaussian4d* __restrict__ out) {
+    __shared__ float s_m[PHD_DYN_FIELDS][EAP4_PASS];
+    const int lane = threadIdx.x;
+    const int g = blockIdx.x;
+    const int a = gstart[g], b = gstart[g + 1];
+    const unsigned int si = ord[mem[a]];
+    phd_eap4_acc acc;
+    float sw = 0.f, sm[4], sc[16];
+    if (lane == 0) {
+        sw = comp[si];
+        for (int i = 0; i < 4; i++) sm[i] = comp[(size_t)(1 + i) * K + si];
+        for (int i = 0; i < 16; i++) sc[i] = comp[(size_t)(5 + i) * K + si];
+        phd_eap4_mean_begin(acc, sw, sm);
+    }
+    for (int pass = 0; pass < 2; pass++) {
+        if (pass == 1 && lane == 0) phd_eap4_cov_begin(acc, sw, sm, sc);
+        const int nf = pass == 0 ? 5 : PHD_DYN_FIELDS;  // the mean pass reads the weight and the mean only
+        for (int c0 = a + 1; c0 < b; c0 += EAP4_PASS) {
+            const int cn = min(EAP4_PASS, b - c0);
+            if (lane < cn) {
+                const unsigned int bi = ord[mem[c0 + lane]];
+                for (int f = 0; f < nf; f++) s_m[f][lane] = comp[(size_t)f * K + bi];
+            }
+            __syncthreads();
+            if (lane == 0) {
+                for (int k = 0; k < cn; k++) {
+                    float bm[4], bc[16];
+                    for (int i = 0; i < 4; i++) bm[i] = s_m[1 + i][k];
+                    if (pass == 0) {
+                        phd_eap4_mean_add(acc, s_m[0][k], bm);
+                    } else {
+                        for (int i = 0; i < 16; i++) bc[i] = s_m[5 + i][k];
+                        phd_eap4_cov_add(acc, s_m[0][k], bm, bc);
+                    }
+                }
+            }
+            __syncthreads();  // (the staging rows are rewritten next)
+        }
+    }
+    if (lane == 0) phd_eap4_finish(acc, out + g);
+}
+
 /* ------------------------------------------------------------------ host */
 
 #define E4CHK(expr)                      \
@@ -703,6 +954,14 @@ struct Eap4Bufs {
     unsigned char* flag;
     phd_gaussian4d* out;
     int* nout;
+    // the decision rounds
+    unsigned int* misc;              // [0] Λ bits [1] fallback flag [2] occupied cells [3] positions waiting
+    unsigned long long *key, *key2;  // cell keys by position / sorted; later the seed keys and slots
+    int *cnt, *run, *gstart;         // cell counts (later the seed flags), cell runs, group starts
+    int* nb9;                        // 9 neighbour cells of every occupied cell
+    float4* rec;                     // 4 planes of K: the records in cell order
+    int4* work;                      // the rounds' work items
+    int *state, *state_t;            // decisions by position / by cell order
     void* tmp;  // hipcub temporary storage
     size_t tmp_bytes;
 };
@@ -723,6 +982,17 @@ static size_t eap4_carve(char* base, long K, size_t tmp, Eap4Bufs* b) {
     t.flag = (unsigned char*)take((size_t)K);
     t.out = (phd_gaussian4d*)take((size_t)K * sizeof(phd_gaussian4d));
     t.nout = (int*)take(4);
+    t.misc = (unsigned int*)take(8 * 4);
+    t.key = (unsigned long long*)take((size_t)K * 8);
+    t.key2 = (unsigned long long*)take((size_t)K * 8);
+    t.cnt = (int*)take((size_t)K * 4);
+    t.run = (int*)take((size_t)(K + 1) * 4);
+    t.gstart = (int*)take((size_t)(K + 1) * 4);
+    t.nb9 = (int*)take((size_t)K * 9 * 4);
+    t.rec = (float4*)take((size_t)K * 4 * sizeof(float4));
+    t.work = (int4*)take(((size_t)K + (size_t)K / EAP4R_NT + 2) * sizeof(int4));
+    t.state = (int*)take((size_t)K * 4);
+    t.state_t = (int*)take((size_t)K * 4);
     t.tmp = take(tmp);
     t.tmp_bytes = tmp;
     if (b) *b = t;
@@ -733,23 +1003,151 @@ static size_t eap4_sort_tmp(long K, hipStream_t st) {
     size_t tmp = 0;
     hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp, (float*)nullptr, (float*)nullptr,
                                                  (unsigned int*)nullptr, (unsigned int*)nullptr, (int)K, 0, 32, st);
+    // the decision rounds' sorts (by cell, by seed), the cells' run-length encode and the seeds' scan
+    size_t t2 = 0;
+    hipcub::DeviceRadixSort::SortPairs(nullptr, t2, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                       (unsigned int*)nullptr, (unsigned int*)nullptr, (int)K, 0, 64, st);
+    tmp = std::max(tmp, t2);
+    hipcub::DeviceRadixSort::SortPairs(nullptr, t2, (unsigned int*)nullptr, (unsigned int*)nullptr,
+                                       (unsigned int*)nullptr, (unsigned int*)nullptr, (int)K, 0, 32, st);
+    tmp = std::max(tmp, t2);
+    hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                          (int*)nullptr, (int*)nullptr, (int)K, st);
+    tmp = std::max(tmp, t2);
+    hipcub::DeviceScan::ExclusiveSum(nullptr, t2, (int*)nullptr, (int*)nullptr, (int)K, st);
+    tmp = std::max(tmp, t2);
     return tmp;
 }
 
-/* The reduce of a prepared SoA (B.comp: the single context's gather, or the
- * concatenated blocks of the sharded form): the iota, the stable descending
- * radix sort, k_eap4_merge, the count read back and the copy out.  Returns the
- * component count (nothing copied when out is NULL or too small), -1 (err). */
-static long eap4_reduce(hipStream_t st, const Eap4Bufs& B, long K, float T, phd_gaussian4d* out, long out_cap,
+static int eap4_bits_for(unsigned int v) {  // radix bits covering 0..v
+    int b = 1;
+    while (b < 32 && (v >> b) != 0) b++;
+    return b;
+}
+
+/* The decision rounds of a prepared, priority-sorted SoA of bound Λ (finite,
+ * positive; T too): cells, rounds, groups and sums, the merged components left
+ * in B.out in emission order.  Returns their count, -1 (err). */
+static long eap4_rounds(hipStream_t st, const Eap4Bufs& B, long K, float lam, float T, int* rounds, int* cells,
                         std::string& err) {
-    hipLaunchKernelGGL(k_eap4_iota, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, B.i0, K);
+    const int Ki = (int)K;
+    const unsigned int nb = (unsigned int)((K + 255) / 256);
+    size_t tb;
+    const double R = std::sqrt(1.05 * (double)T * (double)lam) * 1.0001;
+    const float invR = (float)(1.0 / R);
+    unsigned long long* keyp = B.key;   // cell key by position, then the unique occupied cells
+    unsigned long long* keys = B.key2;  // cell keys sorted
+    unsigned int* pos_by_cell = B.mem;  // positions grouped by cell, ascending within a cell
+    hipLaunchKernelGGL(k_eap_poskey, dim3(nb), dim3(256), 0, st, B.comp, K, B.ord, invR, keyp, B.i0);
+    tb = B.tmp_bytes;
+    E4CHK(hipcub::DeviceRadixSort::SortPairs(B.tmp, tb, keyp, keys, B.i0, pos_by_cell, Ki, 0, 64, st));
+    tb = B.tmp_bytes;
+    E4CHK(hipcub::DeviceRunLengthEncode::Encode(B.tmp, tb, keys, keyp, B.cnt, (int*)B.misc + 2, Ki, st));
+    int ncell = 0;
+    E4CHK(hipMemcpyAsync(&ncell, (int*)B.misc + 2, sizeof(int), hipMemcpyDeviceToHost, st));
+    E4CHK(hipStreamSynchronize(st));
+    // cell runs and the rounds' work items (cell, first index, count): chunks of EAP4R_NT
+    std::vector<int> cnt(ncell), runh(ncell + 1, 0);
+    E4CHK(hipMemcpyAsync(cnt.data(), B.cnt, ncell * sizeof(int), hipMemcpyDeviceToHost, st));
+    E4CHK(hipStreamSynchronize(st));
+    std::vector<int4> work;
+    work.reserve((size_t)ncell + (size_t)(K / EAP4R_NT) + 1);
+    for (int c = 0; c < ncell; c++) {
+        runh[c + 1] = runh[c] + cnt[c];
+        for (int q = 0; q < cnt[c]; q += EAP4R_NT)
+            work.push_back(make_int4(c, runh[c] + q, std::min(EAP4R_NT, cnt[c] - q), 0));
+    }
+    E4CHK(hipMemcpyAsync(B.run, runh.data(), (ncell + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    E4CHK(hipMemcpyAsync(B.work, work.data(), work.size() * sizeof(int4), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_eap_nb9, dim3((ncell + 255) / 256), dim3(256), 0, st, keyp, ncell, B.nb9);
+    hipLaunchKernelGGL(k_eap4_cellrec, dim3(nb), dim3(256), 0, st, B.comp, K, B.ord, pos_by_cell, B.rec);
+    E4CHK(hipMemsetAsync(B.state_t, 0xff, K * sizeof(int), st));  // -1: undecided
+    // decision rounds until no position waits: the waiting is here, between launches
+    // (each round decides at least the highest-priority undecided position)
+    int nr = 1;
+    for (;; nr++) {
+        E4CHK(hipMemsetAsync((int*)B.misc + 3, 0, sizeof(int), st));
+        hipLaunchKernelGGL(k_eap4_lfmis, dim3((unsigned)work.size()), dim3(EAP4R_NT), 0, st, B.work, B.rec, K, B.nb9,
+                           B.run, T, B.state_t, (int*)B.misc + 3);
+        E4CHK(hipGetLastError());
+        int waiting = 0;
+        E4CHK(hipMemcpyAsync(&waiting, (int*)B.misc + 3, sizeof(int), hipMemcpyDeviceToHost, st));
+        E4CHK(hipStreamSynchronize(st));
+        if (waiting == 0) break;
+        if (nr > Ki) {
+            err = "decision rounds did not converge";
+            return -1;
+        }
+    }
+    hipLaunchKernelGGL(k_eap_state_pos, dim3(nb), dim3(256), 0, st, B.state_t, pos_by_cell, K, B.state);
+    // seeds' slots (priority order), members grouped by seed (stable: priority order within a group)
+    int* flag = B.cnt;                           // (the cell counts are dead)
+    unsigned int* skey = (unsigned int*)B.key;   // seed position of every position (the cells are dead)
+    int* slot = (int*)B.key + K;                 // seed slot = seeds before it
+    unsigned int* skey2 = (unsigned int*)B.key2;
+    unsigned int* mem = pos_by_cell;             // positions grouped by seed, ascending within a group
+    hipLaunchKernelGGL(k_eap_seedkey, dim3(nb), dim3(256), 0, st, B.state, K, flag, skey);
+    tb = B.tmp_bytes;
+    E4CHK(hipcub::DeviceScan::ExclusiveSum(B.tmp, tb, flag, slot, Ki, st));
+    int last[2] = {0, 0};
+    E4CHK(hipMemcpyAsync(&last[0], slot + (K - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    E4CHK(hipMemcpyAsync(&last[1], flag + (K - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_iota_u32, dim3(nb), dim3(256), 0, st, B.i0, K);
+    tb = B.tmp_bytes;
+    E4CHK(hipcub::DeviceRadixSort::SortPairs(B.tmp, tb, skey, skey2, B.i0, mem, Ki, 0,
+                                             eap4_bits_for((unsigned int)(K - 1)), st));
+    E4CHK(hipStreamSynchronize(st));
+    const int nout = last[0] + last[1];
+    hipLaunchKernelGGL(k_eap_gstart, dim3(nb), dim3(256), 0, st, skey2, slot, K, nout, B.gstart);
+    hipLaunchKernelGGL(k_eap4_sum, dim3(nout), dim3(64), 0, st, B.comp, K, B.ord, mem, B.gstart, B.out);
+    E4CHK(hipGetLastError());
+    *rounds = nr;
+    *cells = ncell;
+    return nout;
+}
+
+/* The reduce of a prepared SoA (B.comp: the single context's gather, or the
+ * concatenated blocks of the sharded form — both callers come through here,
+ * so Λ and the flag are one function of the same bytes): the bound pass, the
+ * iota and the stable descending radix sort, then the decision rounds
+ * (eap4_rounds), or k_eap4_merge's one workgroup when mode is 1, the flag is
+ * set, or Λ or T is not finite and positive (the static map's one_group rule);
+ * the copy out.  *rounds / *cells: the decision rounds and the occupied cells
+ * (1, 0 for the one-workgroup form).  Returns the component count (nothing
+ * copied when out is NULL or too small), -1 (err). */
+static long eap4_reduce(hipStream_t st, const Eap4Bufs& B, long K, float T, int mode, phd_gaussian4d* out,
+                        long out_cap, int* rounds, int* cells, std::string& err) {
+    const unsigned int nb = (unsigned int)((K + 255) / 256);
+    bool one_group = mode != 0 || !(T > 0.f) || !(T < INFINITY);
+    float lam = 0.f;
+    if (!one_group) {
+        E4CHK(hipMemsetAsync(B.misc, 0, 8 * sizeof(unsigned int), st));
+        hipLaunchKernelGGL(k_eap4_bound, dim3(nb), dim3(256), 0, st, B.comp, K, B.misc, (int*)B.misc + 1);
+    }
+    hipLaunchKernelGGL(k_eap4_iota, dim3(nb), dim3(256), 0, st, B.i0, K);
     size_t tb = B.tmp_bytes;
     E4CHK(hipcub::DeviceRadixSort::SortPairsDescending(B.tmp, tb, B.comp, B.wsorted, B.i0, B.ord, (int)K, 0, 32, st));
-    hipLaunchKernelGGL(k_eap4_merge, dim3(1), dim3(EAP4_NT), 0, st, B.comp, K, B.ord, T, B.flag, B.mem, B.out, B.nout);
-    E4CHK(hipGetLastError());
+    if (!one_group) {
+        unsigned int misc[2];
+        E4CHK(hipMemcpyAsync(misc, B.misc, sizeof(misc), hipMemcpyDeviceToHost, st));
+        E4CHK(hipStreamSynchronize(st));
+        memcpy(&lam, &misc[0], 4);
+        one_group = misc[1] != 0 || !(lam > 0.f) || !(lam < INFINITY);
+    }
     int cnt = 0;
-    E4CHK(hipMemcpyAsync(&cnt, B.nout, 4, hipMemcpyDeviceToHost, st));
-    E4CHK(hipStreamSynchronize(st));
+    if (one_group) {
+        hipLaunchKernelGGL(k_eap4_merge, dim3(1), dim3(EAP4_NT), 0, st, B.comp, K, B.ord, T, B.flag, B.mem, B.out,
+                           B.nout);
+        E4CHK(hipGetLastError());
+        E4CHK(hipMemcpyAsync(&cnt, B.nout, 4, hipMemcpyDeviceToHost, st));
+        E4CHK(hipStreamSynchronize(st));
+        *rounds = 1;
+        *cells = 0;
+    } else {
+        const long n = eap4_rounds(st, B, K, lam, T, rounds, cells, err);
+        if (n < 0) return -1;
+        cnt = (int)n;
+    }
     if (out && cnt <= out_cap) {
         E4CHK(hipMemcpyAsync(out, B.out, (size_t)cnt * sizeof(phd_gaussian4d), hipMemcpyDeviceToHost, st));
         E4CHK(hipStreamSynchronize(st));
@@ -759,7 +1157,8 @@ static long eap4_reduce(hipStream_t st, const Eap4Bufs& B, long K, float T, phd_
 
 long mixed_expected_map_dynamic(hipStream_t st, const int* d_src, const float* d_dmap, const int* d_dsize,
                                 const float* d_dmap_x, const int* d_dsize_x, int n, int dcap, const float* d_logw, float T, phd_gaussian4d* out, long out_cap,
-                                std::string& err) {
+                                int mode, int* rounds, int* cells, std::string& err) {
+    *rounds = *cells = 0;
     std::vector<int> off;
     const long K = eap4_offsets(st, d_src, d_dsize, d_dmap_x ? d_dsize_x : nullptr, n, dcap, off, err);
     if (K <= 0) return K;
@@ -778,7 +1177,7 @@ long mixed_expected_map_dynamic(hipStream_t st, const int* d_src, const float* d
     if (hipMemcpyAsync(d_off, off.data(), (n + 1) * 4, hipMemcpyHostToDevice, st) == hipSuccess) {
         hipLaunchKernelGGL(k_eap4_gather, dim3(n), dim3(256), 0, st, d_src, d_dmap, d_dmap_x, d_off, d_logw, dcap, K,
                            B.comp);
-        nout = eap4_reduce(st, B, K, T, out, out_cap, err);
+        nout = eap4_reduce(st, B, K, T, mode, out, out_cap, rounds, cells, err);
     } else {
         err = hipGetErrorString(hipGetLastError());
     }
@@ -850,7 +1249,9 @@ int eap4_shard_pack(Eap4Scratch** sp, hipStream_t st, const int* d_src, const fl
 }
 
 long mixed_expected_map_dynamic_blocks(Eap4Scratch** sp, hipStream_t st, const void* d_blocks, int world, int n,
-                                       long K_max, float T, phd_gaussian4d* out, long out_cap, std::string& err) {
+                                       long K_max, float T, phd_gaussian4d* out, long out_cap, int mode, int* rounds,
+                                       int* cells, std::string& err) {
+    *rounds = *cells = 0;
     if (!*sp) *sp = new Eap4Scratch();
     Eap4Scratch& S = **sp;
     if (S.heads_world < world) {
@@ -891,7 +1292,7 @@ long mixed_expected_map_dynamic_blocks(Eap4Scratch** sp, hipStream_t st, const v
     eap4_carve(S.buf, K, tmp, &B);
     eap_launch_concat(st, d_blocks, stride_words, PHD_DYN_FIELDS, world, K_max, d_off, K, B.comp);
     E4CHK(hipGetLastError());
-    return eap4_reduce(st, B, K, T, out, out_cap, err);
+    return eap4_reduce(st, B, K, T, mode, out, out_cap, rounds, cells, err);
 }
 
 #undef E4CHK

@@ -81,10 +81,14 @@ hipError_t mixed_set_lds_limit();
 
 /* EAP map of the dynamic maps of n particles (exp_map_dynamic): the component
  * count (nothing copied when out is NULL or too small), -1 on a HIP error;
- * d_dmap_x / d_dsize_x: the dynamic set X (NULL: no reference names it) */
+ * d_dmap_x / d_dsize_x: the dynamic set X (NULL: no reference names it).
+ * mode 0: decision rounds over the whole GPU (the one workgroup for inputs the
+ * lattice bound does not cover), 1: the one workgroup only — the same bytes.
+ * *rounds / *cells: the decision rounds and occupied lattice cells of this
+ * call (1, 0 for the one-workgroup form; 0, 0 for an empty set). */
 long mixed_expected_map_dynamic(hipStream_t st, const int* d_src, const float* d_dmap, const int* d_dsize,
                                 const float* d_dmap_x, const int* d_dsize_x, int n, int dcap, const float* d_logw, float T, phd_gaussian4d* out, long out_cap,
-                                std::string& err);
+                                int mode, int* rounds, int* cells, std::string& err);
 
 /* The sharded form (the "EAP4" block: include/phd_capi.h).  eap4_shard_count:
  * the dynamic components of the store, clamped per particle to dcap (-1: a HIP
@@ -104,7 +108,8 @@ int eap4_shard_pack(Eap4Scratch** sp, hipStream_t st, const int* d_src, const fl
                     const float* d_dmap_x, const int* d_dsize_x, const float* d_logw, int n, int dcap, long K_max,
                     void* d_block, std::string& err);
 long mixed_expected_map_dynamic_blocks(Eap4Scratch** sp, hipStream_t st, const void* d_blocks, int world, int n,
-                                       long K_max, float T, phd_gaussian4d* out, long out_cap, std::string& err);
+                                       long K_max, float T, phd_gaussian4d* out, long out_cap, int mode, int* rounds,
+                                       int* cells, std::string& err);
 
 }  // namespace phd
 

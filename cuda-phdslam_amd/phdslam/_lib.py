@@ -129,6 +129,8 @@ SIGNATURES = {
     "phd_write_state_log": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, _vp, _vp, ctypes.c_long, _vp, _vp,
                                            ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "phd_expected_map_groups": (ctypes.c_int, [_vp, _c_int_p]),
+    "phd_expected_map_dynamic_groups": (ctypes.c_int, [_vp, _c_int_p, _c_int_p]),
+    "phd_set_expected_map_dynamic_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
     "phd_last_update_ms": (ctypes.c_int, [_vp, _c_float_p]),
     "phd_enable_timing": (ctypes.c_int, [_vp, ctypes.c_int]),
     "phd_set_timing_stride": (ctypes.c_int, [_vp, ctypes.c_int]),

@@ -463,6 +463,13 @@ class ShardedFilter:
         (expected_map_phases, on buffers of its own)."""
         return self._serve(self.expected_map_phases(True))
 
+    def expected_map_dynamic_groups(self):
+        """(rounds, cells) of the last expected_map_dynamic (the single context's cells)."""
+        return self.f.expected_map_dynamic_groups()
+
+    def set_expected_map_dynamic_mode(self, mode):
+        self.f.set_expected_map_dynamic_mode(mode)
+
     def receive(self):
         """After the all-to-all of the blocks into recv_blocks."""
         self.f.shard_receive_blocks(self.recv_blocks.data_ptr(), self.K, self.recv_rec.data_ptr())
@@ -734,6 +741,12 @@ class GroupRank:
                                                                    ctypes.byref(nout)),
                      "phd_group_expected_map_dynamic")
         return out[:nout.value].copy()
+
+    def expected_map_dynamic_groups(self):
+        return self.f.expected_map_dynamic_groups()
+
+    def set_expected_map_dynamic_mode(self, mode):
+        self.f.set_expected_map_dynamic_mode(mode)
 
     @property
     def stats(self):

@@ -387,6 +387,21 @@ class PHDFilter:
         _lib.check(_lib.lib().phd_expected_map_groups(self._h, ctypes.byref(g)), "phd_expected_map_groups")
         return g.value
 
+    def expected_map_dynamic_groups(self):
+        """(rounds, cells) of the last expected_map_dynamic, single or blocks form
+        (phd_expected_map_dynamic_groups): the decision rounds and the occupied
+        lattice cells; (1, 0) for the one-workgroup form, (0, 0) before any call."""
+        r, c = ctypes.c_int(), ctypes.c_int()
+        _lib.check(_lib.lib().phd_expected_map_dynamic_groups(self._h, ctypes.byref(r), ctypes.byref(c)),
+                   "phd_expected_map_dynamic_groups")
+        return r.value, c.value
+
+    def set_expected_map_dynamic_mode(self, mode):
+        """0: decision rounds over the whole GPU (default); 1: the one-workgroup
+        form only.  The same bytes either way."""
+        _lib.check(_lib.lib().phd_set_expected_map_dynamic_mode(self._h, int(mode)),
+                   "phd_set_expected_map_dynamic_mode")
+
     def last_update_ms(self):
         v = ctypes.c_float()
         _lib.check(_lib.lib().phd_last_update_ms(self._h, ctypes.byref(v)), "phd_last_update_ms")

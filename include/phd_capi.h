@@ -337,8 +337,25 @@ int phd_cardinalities(phd_ctx* ctx, float* cn_host);
 int phd_expected_map(phd_ctx* ctx, phd_gaussian2d* out, long out_cap, long* n_out);
 /* EAP map of the dynamic (Gaussian4D) maps, feature_model 2: recoverSlamState's
  * exp_map_dynamic (main.cpp:369-371 -> gm_reduce.cpp:59-132, 4-D LLT distance).
- * Same conventions as phd_expected_map. */
+ * Same conventions as phd_expected_map.  The greedy runs as phd_expected_map's
+ * does: a stable priority sort, lattice cells over the two position
+ * coordinates (side sqrt(1.05 T Λ), Λ the largest covariance trace), decision
+ * rounds over the whole GPU, one wave per seed for the moment sums — byte for
+ * byte and in emission order what one workgroup running the serial greedy
+ * gives.  That one-workgroup form serves the inputs the lattice bound does not
+ * cover: a non-finite field, a negative variance or a positive one below
+ * 2^-60, no positive finite trace, or a T that is not finite and positive.  A
+ * finite covariance that is not positive definite stays on the rounds (its
+ * pairs never merge in either form). */
 int phd_expected_map_dynamic(phd_ctx* ctx, phd_gaussian4d* out, long out_cap, long* n_out);
+/* Decision rounds and occupied lattice cells of this context's last dynamic
+ * expected map, single or blocks form (diagnostic; does not synchronise).  The
+ * one-workgroup form reports rounds = 1, cells = 0; both are 0 before any call
+ * and after a call on an empty set. */
+int phd_expected_map_dynamic_groups(phd_ctx* ctx, int* rounds, int* cells);
+/* 0 (default): the decision rounds; 1: the one-workgroup form only (the same
+ * bytes; there so both can be compared and timed).  Anything else: PHD_E_ARG. */
+int phd_set_expected_map_dynamic_mode(phd_ctx* ctx, int mode);
 /* Synchronous decision rounds of the last phd_expected_map (diagnostic; 1 for
  * the single-workgroup fallback of non-finite inputs). */
 int phd_expected_map_groups(phd_ctx* ctx, int* groups);
@@ -406,9 +423,10 @@ int phd_expected_map_blocks(phd_ctx* ctx, const void* dev_blocks, int world, lon
  * order over every particle, ties by concatenation index), so here too the
  * inputs travel: every rank packs its weighted dynamic components into a
  * block, the caller all-gathers the blocks in rank order, and every rank
- * concatenates them and runs phd_expected_map_dynamic's own reduce (a stable
- * sort and ONE workgroup whose result depends on the concatenated component
- * array alone).  Every rank then holds, byte for byte and in the same emission
+ * concatenates them and runs phd_expected_map_dynamic's own reduce (the bound
+ * pass, the stable sort and the decision rounds, or the one workgroup: all of
+ * it a function of the concatenated component array alone, Λ included, so the
+ * header carries no bound).  Every rank then holds, byte for byte and in the same emission
  * order, what phd_expected_map_dynamic returns on a single mixed context of
  * world * n particles loaded with the ranks' settled stores in rank order
  * (rank 0's slots 0 .. n-1, then rank 1's, ...; each particle's components in
@@ -441,8 +459,11 @@ int phd_expected_map_blocks(phd_ctx* ctx, const void* dev_blocks, int world, lon
  * demand) and reduces it; out / out_cap / n_out as phd_expected_map_dynamic
  * (*n_out written whenever the reduce ran; PHD_E_CAPACITY with nothing copied
  * when out is NULL or too small; n_out = 0 for an empty set), T = minSeparation
- * of the context's config.  It synchronises.  Its time is the one-workgroup
- * reduce's, which grows with the whole filter's dynamic component count.
+ * of the context's config.  It synchronises.  Every rank reduces the whole set:
+ * about 340 bytes of scratch per component per rank, and the decision rounds'
+ * time, which grows roughly with the component count (the one-workgroup form's
+ * grows with seeds x components); phd_expected_map_dynamic_groups reports the
+ * rounds and cells, phd_set_expected_map_dynamic_mode selects the form.
  * PHD_E_ARG, before anything is written or any field is read: no
  * phd_set_config, no phd_enable_dynamic; a null or 16-byte-misaligned buffer;
  * K_max outside [0, 2^31 - 1); a store with more than K_max dynamic components

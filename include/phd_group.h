@@ -104,8 +104,10 @@ int phd_group_expected_map(phd_group* g, phd_gaussian2d* out, long out_cap, long
  * phases of phd_group_expected_map on buffers of its own: the settle,
  * ncclAllGather of the counts (phd_eap_dyn_shard_count), phd_eap_dyn_shard_pack,
  * one ncclAllGather of the blocks (84 K_max + 64 bytes per rank, kept), and
- * phd_expected_map_dynamic_blocks on every rank of this process.  On such a
- * group phd_group_expected_map returns the static expected map.  Synchronises. */
+ * phd_expected_map_dynamic_blocks on every rank of this process (the decision
+ * rounds over each rank's whole GPU; phd_set_expected_map_dynamic_mode and
+ * phd_expected_map_dynamic_groups on a rank's context select the form and
+ * report its rounds and cells).  On such a group phd_group_expected_map returns the static expected map.  Synchronises. */
 int phd_group_expected_map_dynamic(phd_group* g, phd_gaussian4d* out, long out_cap, long* n_out);
 /* Counters over the steps so far: [0] resamples, [1] migrated particles,
  * [2] records sent, [3] records beyond the fixed blocks, [4] pending slots. */

@@ -5,6 +5,21 @@ single context holding the same components (DESIGN.md §6 "Mixed model",
 wall clock around synchronised calls, median / min / max in ms, one JSON line.
 
     python scripts/time_eap_dynamic.py
+
+The two forms of the reduce itself (DESIGN.md §6 "Mixed model", *Decision
+rounds*): `rounds` builds a mixed store of n particles x 64 dynamic components
+drawn from 3 000 landmarks spread over a 400 x 400 square (so the map has a few
+thousand components), and calls expected_map_dynamic() in mode 1 (the one
+workgroup) and mode 0 (the decision rounds) alternately: the median of five
+calls after the first, with rounds, cells and the output count, and whether
+the two maps are the same bytes.  Two shapes, n = 256 and n = 4 096.  The
+mode-1 calls of a shape stop once they have used MODE1_BUDGET_S in all; a
+shape that could not finish its six is reported "exceeded".  --tree names
+another checkout (a built worktree of the parent commit) whose library is
+timed instead; one without the mode switch is timed as it is.
+
+    timeout -k 10 900 python scripts/time_eap_dynamic.py rounds
+    timeout -k 10 300 python scripts/time_eap_dynamic.py rounds --tree ../parent --shapes 256
 """
 import json
 import os
@@ -15,6 +30,8 @@ import time
 import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--tree" in sys.argv:  # (before the import of phdslam: the other checkout's package and library)
+    REPO = os.path.abspath(sys.argv[sys.argv.index("--tree") + 1])
 sys.path[:0] = [os.path.join(REPO, "cuda-phdslam_amd"), os.path.join(REPO, "tests")]
 
 import torch  # noqa: E402
@@ -83,6 +100,82 @@ def shape(world, n, gd, dcap, kcap, reps):
     return res
 
 
+MODE1_BUDGET_S = 240.0
+LANDMARKS, PER, CALLS = 3000, 64, 6
+
+
+def rounds_store(n, seed=9):
+    """n particles x PER components, each a jittered copy of one of LANDMARKS
+    landmarks (a particle sees a random subset), weights and log-weights random."""
+    from phdslam.types import GAUSSIAN4D
+    rng = np.random.default_rng(seed)
+    base = np.concatenate([rng.uniform(-200, 200, (LANDMARKS, 2)), rng.normal(0, 1.5, (LANDMARKS, 2))], 1)
+    K = n * PER
+    pick = np.concatenate([rng.choice(LANDMARKS, PER, replace=False) for _ in range(n)])
+    d = np.zeros(K, GAUSSIAN4D)
+    d["mean"] = (base[pick] + rng.normal(0, 0.1, (K, 4))).astype(np.float32)
+    cov = np.zeros((K, 4, 4))
+    cov[:, 0, 0], cov[:, 1, 1] = rng.uniform(0.05, 0.3, K), rng.uniform(0.05, 0.3, K)
+    cov[:, 2, 2], cov[:, 3, 3] = rng.uniform(0.2, 1.0, K), rng.uniform(0.2, 1.0, K)
+    cov[:, 0, 2] = cov[:, 2, 0] = rng.uniform(-0.02, 0.02, K)
+    cov[:, 1, 3] = cov[:, 3, 1] = rng.uniform(-0.02, 0.02, K)
+    d["cov"] = cov.transpose(0, 2, 1).reshape(K, 16)
+    d["weight"] = rng.uniform(0.2, 1.0, K)
+    lw = rng.normal(-np.log(n), 0.3, n).astype(np.float32)
+    return d, np.arange(n + 1, dtype=np.int32) * PER, lw
+
+
+def rounds_shape(n):
+    cfg = mixed_config()
+    poses, sm, sof, _, _, _ = mixed_scenario(cfg, n, 3, 1, 4)
+    dm, dof, lw = rounds_store(n)
+    f = filt(cfg, n, PER, 256)
+    f.load(poses, lw, sm, sof)
+    f.load_dynamic(dm, dof)
+    modes = (1, 0) if hasattr(f, "set_expected_map_dynamic_mode") else (None,)
+    ts, maps, diag = {m: [] for m in modes}, {}, {}
+    spent1 = 0.0
+    for _ in range(CALLS):
+        for m in modes:
+            if m == 1 and spent1 > MODE1_BUDGET_S:
+                continue
+            if m is not None:
+                f.set_expected_map_dynamic_mode(m)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            maps[m] = f.expected_map_dynamic()
+            torch.cuda.synchronize()
+            ts[m].append((time.perf_counter() - t0) * 1e3)
+            if m == 1:
+                spent1 += ts[m][-1] * 1e-3
+            if m is not None:
+                diag[m] = f.expected_map_dynamic_groups()
+    res = {"n": n, "components": n * PER, "tree": "--tree" if "--tree" in sys.argv else "this tree"}
+    for m in modes:
+        name = {1: "one_workgroup", 0: "rounds", None: "as_built"}[m]
+        t = ts[m][1:]
+        if len(ts[m]) < CALLS:
+            res[name] = {"exceeded": True, "calls_ms": [round(x, 2) for x in ts[m]], "budget_s": MODE1_BUDGET_S}
+        else:
+            res[name] = {"median_ms": round(statistics.median(t), 3), "min_ms": round(min(t), 3),
+                         "max_ms": round(max(t), 3), "first_ms": round(ts[m][0], 3), "reps": len(t)}
+        if m in maps:
+            res[name]["out_components"] = len(maps[m])
+        if m in diag:
+            res[name]["rounds"], res[name]["cells"] = diag[m]
+    if 0 in maps and 1 in maps:
+        res["equal"] = maps[0].tobytes() == maps[1].tobytes()
+    f.close()
+    return res
+
+
 if __name__ == "__main__":
-    out = [shape(2, 24, 10, 64, 4096, 30), shape(8, 512, 10, 16, 256, 7)]
-    print(json.dumps(out))
+    if "rounds" in sys.argv[1:]:
+        ns = [256, 4096]
+        if "--shapes" in sys.argv:
+            ns = [int(x) for x in sys.argv[sys.argv.index("--shapes") + 1].split(",")]
+        for n in ns:
+            print(json.dumps(rounds_shape(n)), flush=True)
+    else:
+        out = [shape(2, 24, 10, 64, 4096, 30), shape(8, 512, 10, 16, 256, 7)]
+        print(json.dumps(out))
